@@ -42,6 +42,11 @@ resident in HBM: [T][39] floats in, [T][3000] log10 likelihoods out.
              bounded sample of the same workload: one host core, an N-process figure (C2: eager scoring; C3 / C4: 16 julius
              -1pass processes side by side), the full two-pass recogniser on a few of the same files, DNN num_threads 2 / half the cores.
 
+A plain run (`bench.py --gpus 1 --steps K --warmup W`) measures the top level alone: set-up, W warm-up steps, K timed
+steps, the result line.  `--full` is the whole tree above: the nested configurations (--workload all), k1_small_T and
+the CPU baselines / parity legs of the compiled reference.  `--dump-outputs DIR` writes a seeded sample of the top-level
+step's output after the timed steps (dump_outputs()).
+
 Multi-GPU: one process per GPU; utterances are sharded, no data-path collective ("weak" scaling:
 per-GPU batch fixed; `e2e_strong` / `--workload e2e --strong` = the fixed 512-utterance batch).  RCCL is used for the barrier, the max-over-ranks clock and the gather of the
 per-utterance result records (julius_amd/shard.py).  `--gpus N` without a torch.distributed.run
@@ -74,9 +79,13 @@ S, M, D = 3000, 16, 39
 FRAMES_PER_UTT = 1000
 LAUNCHES_PER_STEP = 12         # C2: one step = 12 sub-batches of --utts utterances (>= 100 ms of kernel time per step)
 C5_TOTAL_UTTS = 512            # BASELINE.json configs[4]: the fixed batch that is sharded over the GPUs
+DUMP_ROWS = 4096               # --dump-outputs: a fixed, seeded sample of the step's score rows (4096 x 3000 x 4 B = 49 MB)
 HBM_PEAK_GBS = 8000.0          # MI355X_MICROARCH.md: 8 TB/s spec
 VALU_PEAK_TOPS = 78.6          # 256 CU x 4 SIMD x 32 lanes x 2.4 GHz, one fp32 op/lane/clk (no FMA allowed)
 MFMA_F32_PEAK = 157.3          # TFLOP/s, dense fp32 MFMA
+# the exporter (julius_amd/shim/jamd_export.c) as oracle/Makefile links it with the reference, next to the compiled reference
+EXPORT = ROOT / "oracle" / "_ref" / "bin" / "jamd_export"
+REF_SO = ROOT / "oracle" / "_ref" / "libjref.so"
 
 
 # ------------------------------------------------------------------------------------------------ dist
@@ -218,6 +227,20 @@ def cpu_baseline_gmm(model, frames, spot, budget=10.0):
     return out, parity
 
 
+def dump_outputs(out_dir, d_out):
+    """--dump-outputs: the last step's [frames][S] log10 likelihoods (9.2 GB at the default size) as a fixed, seeded sample
+    of DUMP_ROWS rows, all S states of each, with the rows' frame indices.  The inputs are seeded, so two builds given the
+    same arguments can be compared output for output."""
+    import torch
+    d = Path(out_dir)
+    d.mkdir(parents=True, exist_ok=True)
+    n = d_out.shape[0]
+    rows = np.sort(np.random.default_rng(0).choice(n, min(n, DUMP_ROWS), replace=False))
+    got = d_out[torch.from_numpy(rows).to(d_out.device)].cpu().numpy()
+    np.save(d / "scores.npy", got.astype(np.float32, copy=False))
+    np.save(d / "scores_rows.npy", rows.astype(np.float64))
+
+
 def run_gmm(args, dd: Dist, steps, warmup):
     """One step = LAUNCHES_PER_STEP sub-batches (each --utts utterances x 1000 frames, its own frames and its own
     [T][S] output rows, all resident in HBM) scored back to back: 12 x 64 000 frames = 768 000 frames x 3000 states
@@ -248,6 +271,8 @@ def run_gmm(args, dd: Dist, steps, warmup):
 
     elapsed, ev = timed_steps(dd, stream, step, steps, warmup, nevents=L + 1)
     kern_ms = float(np.mean([e[l].elapsed_time(e[l + 1]) for e in ev for l in range(L)]))
+    if args.dump_outputs and dd.rank == 0:
+        dump_outputs(args.dump_outputs, d_out)
     res = None
     if dd.rank == 0:
         total_frames = L * T * dd.world * steps
@@ -318,7 +343,7 @@ def run_gmm(args, dd: Dist, steps, warmup):
                              "note": "back-to-back calls on one stream (launch overhead included); model_GBs = the model's bytes per call / "
                                      "time per call: what a frame-synchronous caller streams; the model stays in L2 / Infinity Cache between "
                                      "calls, so this is a rate, not measured HBM traffic"}
-        if dd.world == 1 and not args.no_cpu_baseline:
+        if dd.world == 1 and not args.no_cpu_baseline and REF_SO.exists():
             rng = np.random.default_rng(0)
             ss = np.sort(rng.choice(S, 16, replace=False))
             tt = np.sort(rng.choice(L * T, 64, replace=False))  # 64 full-size rows (any launch of the step) against the compiled reference
@@ -363,7 +388,7 @@ def run_dnn(args, dd: Dist, steps, warmup):
            "config": {"workload": f"C4 scoring half (BASELINE.json configs[3]): DNN {dims}, {T} frames per GPU per step"},
            "roofline": {"bound": "mfma", "achieved": flops / (ms * 1e-3) / 1e12, "peak": MFMA_F32_PEAK, "unit": "TFLOP/s",
                         "frac": flops / (ms * 1e-3) / 1e12 / MFMA_F32_PEAK, "traffic": None, "kernel_ms": ms}}
-    if dd.world == 1 and not args.no_cpu_baseline:
+    if dd.world == 1 and not args.no_cpu_baseline and REF_SO.exists():
         # the compiled reference's dnn_calc_outprob() (FMA path) on a bounded sample; the same rows are the parity check
         from oracle import pyoracle
         with tempfile.TemporaryDirectory(prefix="jamd_dnn_") as td:
@@ -413,11 +438,10 @@ def build_reference_task(workdir: Path, nword: int, beam: int, dnn=None, multipa
         am = ["-dnnconf", task["dnnconf"], "-notypecheck"]
     jargs = ["-h", task["hmmdefs"], "-hlist", task["hmmlist"], "-v", task["dict"], "-nlr", task["arpa"]] + am + [
         "-input", "htkparam", "-1pass", "-b", str(beam)] + (["-multipath"] if multipath else [])
-    export = ROOT / "julius_amd" / "jamd_export"
-    if not export.exists():
+    if not EXPORT.exists():
         return task, jargs, None
     prefix = workdir / "task"
-    subprocess.run([str(export)] + [str(a) for a in jargs] + ["-jamdout", str(prefix)], check=True,
+    subprocess.run([str(EXPORT)] + [str(a) for a in jargs] + ["-jamdout", str(prefix)], check=True,
                    stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
     return task, jargs, prefix
 
@@ -429,11 +453,10 @@ def build_c1_task(workdir: Path, beam: int):
     task = synth.make_grammar_task(workdir, seed=0)
     jargs = ["-h", task["hmmdefs"], "-dfa", task["dfa"], "-v", task["dict"], "-input", "htkparam", "-gprune", "safe", "-tmix", "2",
              "-1pass", "-b", str(beam), "-penalty1", "-1.0"]
-    export = ROOT / "julius_amd" / "jamd_export"
-    if not export.exists():
+    if not EXPORT.exists():
         return task, jargs, None
     prefix = workdir / "task"
-    subprocess.run([str(export)] + [str(a) for a in jargs] + ["-jamdout", str(prefix)], check=True,
+    subprocess.run([str(EXPORT)] + [str(a) for a in jargs] + ["-jamdout", str(prefix)], check=True,
                    stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
     return task, jargs, prefix
 
@@ -576,7 +599,9 @@ def run_e2e(args, dd: Dist, runs, use_dnn=False, flat=False, multipath=False, c1
     if c1 and prefix is None:
         return {}      # (no Julius tree to build jamd_export from: the C1 line needs the reference's grammar loader)
     if multipath and prefix is None:
-        raise SystemExit("bench.py: the multipath workload needs julius_amd/jamd_export (the multipath lexicon is the reference's)")
+        if args.workload == "all":
+            return {}  # (like C1: the nested -multipath lines need the reference's exporter, built with oracle/_ref)
+        raise SystemExit("bench.py: the multipath workload needs oracle/_ref/bin/jamd_export (the multipath lexicon is the reference's)")
     ref_built = prefix is not None
     if ref_built:
         lx = lib.Lexicon.from_file(eng, str(prefix) + ".lex")
@@ -935,10 +960,18 @@ def main():
     ap.add_argument("--no-pipeline", action="store_true",
                     help="e2e: scoring and first pass of every step on ONE stream (default: two streams, the scoring of step k+1 "
                          "overlaps the first pass of step k)")
-    ap.add_argument("--workload", default="all", choices=["all", "gmm", "dnn", "e2e", "e2e-dnn"],
-                    help="all (default) = gmm at top level with e2e (C3), e2e_strong (C5 batch), e2e_dnn (C4) and dnn (C4 scoring "
-                         "half) nested; gmm = BASELINE configs[1] alone; dnn = configs[3] scoring half; e2e = configs[2] "
-                         "(--strong: configs[4]); e2e-dnn = configs[3] end to end")
+    ap.add_argument("--workload", default=None, choices=["all", "gmm", "dnn", "e2e", "e2e-dnn"],
+                    help="all (the default with --full) = gmm at top level with e2e (C3), e2e_strong (C5 batch), e2e_dnn (C4) and "
+                         "dnn (C4 scoring half) nested; gmm = BASELINE configs[1] alone; dnn = configs[3] scoring half; e2e = "
+                         "configs[2] (--strong: configs[4]); e2e-dnn = configs[3] end to end.  Without --full and --workload: the "
+                         "headline alone (the gmm workload's timed steps, no small-T calls, no CPU baseline)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: --workload all by default (the nested configurations, their "
+                         "parity legs and jamd_batch runs), the k1_small_T calls and the CPU baselines of the compiled reference")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the gmm workload's last step computed to DIR/*.npy: a fixed, seeded "
+                         f"sample of {DUMP_ROWS} of its score rows (scores.npy, float32 [rows][{S}]) and their frame indices "
+                         "(scores_rows.npy, float64)")
     ap.add_argument("--beam", type=int, default=None,
                     help="e2e: rank beam (-b; default 800 = the reference's default for triphone models, e2e-dnn: 4000 = the "
                          "reference's DNN recipe)")
@@ -975,6 +1008,12 @@ def main():
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         return spawn_ranks(args)
 
+    if args.workload is None:
+        args.workload = "all" if args.full else "gmm"
+        if not args.full:       # the plain run: the headline's set-up, warm-up and timed steps, nothing else
+            args.no_small_T = args.no_cpu_baseline = True
+    if args.dump_outputs and args.workload not in ("all", "gmm"):
+        raise SystemExit("bench.py: --dump-outputs writes the gmm workload's outputs (--workload gmm or all)")
     dd = Dist(args.gpus, args.dist_backend, args.share_device)
     wl = args.workload
     nested = wl == "all"

@@ -20,6 +20,7 @@ REF_SO = HERE / "_ref" / "libjref.so"
 REF_AMD_SO = HERE / "_ref" / "libjref_amd.so"   # same reference, first pass served by julius_amd/shim
 PLUGIN_DIR = HERE / "_ref" / "plugin"
 REF_O_SO = HERE / "_ref" / "libjref_o.so"       # same reference (own beam), scoring entry points wrapped (boundary O)
+EXPORT = HERE / "_ref" / "bin" / "jamd_export"  # julius_amd/shim/jamd_export.c linked with the reference (oracle/Makefile)
 
 GPRUNE_NONE, GPRUNE_SAFE, GPRUNE_HEU, GPRUNE_BEAM = 0, 1, 2, 3
 # reference enum (libsent/include/sent/hmm_calc.h:45)

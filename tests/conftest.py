@@ -25,10 +25,9 @@ def ref():
     container from /root/reference; travels prebuilt to the GPU box."""
     from oracle import pyoracle
     if not pyoracle.REF_SO.exists():
-        if Path("/root/reference/libsent/src/phmm/outprob.c").exists():
-            pyoracle.build(ref=True)
-        else:
-            pytest.skip("oracle/_ref/libjref.so not built and /root/reference absent")
+        pyoracle.build(ref=True)        # (oracle/Makefile builds it only where the reference tree is readable)
+    if not pyoracle.REF_SO.exists():
+        pytest.skip("oracle/_ref/libjref.so not built and no reference tree to build it from")
     return pyoracle.Ref()
 
 

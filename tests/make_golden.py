@@ -249,6 +249,20 @@ def main_multipath():
     beam_fixture(ref, tmp, "beam_multipath", seed=8, beam=100, extra=["-sepnum", "4", "-bs", "90"], nword=50, trans=trans)
 
 
+def main_refcfg():
+    """The #define sets of the reference's own ./configure (tests/test_refcfg.py), without the build-description and
+    audio-input entries that test leaves out: its stand-in where the reference tree is not readable."""
+    import json
+    sys.path.insert(0, str(ROOT / "tests"))
+    import test_refcfg as t
+    got = {}
+    for lib, hdr in (("libsent", "include/sent/config.h"), ("libjulius", "include/julius/config.h")):
+        d = t.configure_defines(lib, hdr, tempfile.mkdtemp())
+        got[lib] = {k: v for k, v in sorted(d.items()) if k not in t.ALLOWED}
+    (OUT / "refcfg_configure.json").write_text(json.dumps(got, indent=1) + "\n")
+    print("wrote refcfg_configure.json", {k: len(v) for k, v in got.items()})
+
+
 if __name__ == "__main__":
     what = sys.argv[1] if len(sys.argv) > 1 else "all"
     if what in ("am", "all"):
@@ -261,3 +275,5 @@ if __name__ == "__main__":
         main_gms()
     if what in ("rejgmm", "all"):
         main_rejgmm()
+    if what in ("refcfg", "all"):
+        main_refcfg()

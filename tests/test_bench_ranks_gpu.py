@@ -30,8 +30,8 @@ def _run(extra, tmp_path, name):
 
 
 def test_two_ranks_on_one_device_equal_the_single_rank_job(tmp_path):
-    if not (ROOT / "julius_amd" / "jamd_export").exists():
-        pytest.skip("julius_amd/jamd_export not built (the task's lexicon is the reference's)")
+    if not (ROOT / "oracle" / "_ref" / "bin" / "jamd_export").exists():
+        pytest.skip("oracle/_ref/bin/jamd_export not built (the task's lexicon is the reference's)")
     one, z1 = _run([], tmp_path, "n1")
     two, z2 = _run(["--gpus", "2", "--dist-backend", "gloo", "--share-device"], tmp_path, "n2")
     # the fixed batch is dealt round-robin: 6 utterances per rank, rank 0 holds g = 0, 2, 4, ...

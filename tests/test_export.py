@@ -1,6 +1,6 @@
 """CPU: julius_amd/shim/jamd_export.c -- the exporter a Julius maintainer runs once per
 configuration: Julius' own loaders -> "JAMDGMM1" / "JAMDLEX1" files for workers that never link
-Julius.  Built against the unmodified reference by oracle/Makefile (julius_amd/jamd_export);
+Julius.  Built against the unmodified reference by oracle/Makefile (oracle/_ref/bin/jamd_export);
 its files must equal what the tap driver's in-process flattening produces."""
 import subprocess
 
@@ -10,13 +10,13 @@ import pytest
 from julius_amd import lexblob, synth
 from oracle import pyoracle
 
-EXPORT = pyoracle.HERE.parent / "julius_amd" / "jamd_export"
+EXPORT = pyoracle.EXPORT
 
 
 @pytest.mark.parametrize("lm", ["ngram", "grammar", "grammar_forward_dfa"])
 def test_export_program_matches_in_process_flattening(ref, tmp_path, lm):
     if not EXPORT.exists():
-        pytest.skip("julius_amd/jamd_export not built")
+        pytest.skip("oracle/_ref/bin/jamd_export not built")
     task = synth.make_triphone_task(tmp_path, seed=91, nword=60)
     if lm == "ngram":
         args = ["-h", task["hmmdefs"], "-hlist", task["hmmlist"], "-v", task["dict"], "-nlr", task["arpa"],
@@ -56,7 +56,7 @@ def test_export_selection_model(ref, tmp_path):
     """-gshmm: PREFIX.gms holds the flattened selection model, the state map and -gsnum, equal to what
     gms_init() (gms.c:275-317) built inside the reference."""
     if not EXPORT.exists():
-        pytest.skip("julius_amd/jamd_export not built")
+        pytest.skip("oracle/_ref/bin/jamd_export not built")
     task = synth.make_triphone_task(tmp_path, seed=92, nword=60)
     gpath, _ = synth.make_gs_model(task, seed=92)
     args = [str(a) for a in ["-h", task["hmmdefs"], "-hlist", task["hmmlist"], "-v", task["dict"], "-nlr", task["arpa"],
@@ -75,7 +75,7 @@ def test_export_verification_gmms(ref, tmp_path):
     """-gmm / -gmmnum / -gmmreject: PREFIX.rej holds the flattened GMM definitions, the output state of
     every model in recog->gmm->start order, -gmmnum, the names and gc->is_voice[]."""
     if not EXPORT.exists():
-        pytest.skip("julius_amd/jamd_export not built")
+        pytest.skip("oracle/_ref/bin/jamd_export not built")
     task = synth.make_triphone_task(tmp_path, seed=94, nword=60)
     gpath, _, names = synth.make_rejection_gmm(tmp_path, task["model"]["centre"], seed=94, null_frac=0.1)
     args = [str(a) for a in ["-h", task["hmmdefs"], "-hlist", task["hmmlist"], "-v", task["dict"], "-nlr", task["arpa"],
@@ -102,7 +102,7 @@ def test_product_shim_makefile_builds_the_bindings(tmp_path):
     from pathlib import Path
     root = Path(__file__).resolve().parent.parent
     ref = Path(os.environ.get("JULIUS_REF", "/root/reference"))
-    if not (ref / "libsent/include/sent/stddefs.h").exists():
+    if not os.path.isfile(ref / "libsent/include/sent/stddefs.h"):       # (unreadable counts as absent)
         import pytest
         pytest.skip("no Julius source tree on this box")
     subprocess.run(["make", "-s", "-C", str(root / "julius_amd/shim"), "objs", f"JULIUS_SRC={ref}", f"JULIUS_CFG={root / 'oracle/refcfg'}",

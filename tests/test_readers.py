@@ -11,7 +11,7 @@ import pytest
 from julius_amd import lexblob, lib, synth
 from oracle import pyoracle
 
-EXPORT = pyoracle.HERE.parent / "julius_amd" / "jamd_export"
+EXPORT = pyoracle.EXPORT
 
 
 def _ref():

@@ -47,5 +47,5 @@ JAMD_SWEEP_PROF=1 timeout 200 python tools/sweep_timing.py > $O/sweep_timing_rea
 timeout 900 python -m pytest tests -m gpu -q 2>&1 | tail -3 > $O/gpu_tests_final.txt
 bash tools/prof_run.sh ${R}_default --gpus 1 --steps 20 --warmup 5 > /dev/null 2>&1
 cp gpurun_out/prof_${R}_default/summary.json $O/default_command_kernel_trace_summary.json; cp gpurun_out/prof_${R}_default/bench_line.json $O/default_command_bench_line_under_rocprof.json
-python bench.py > $O/bench_default.out 2> $O/bench_default.err; tail -1 $O/bench_default.out > $O/bench_default_final_line.json; cp bench_detail.json $O/bench_default_final_detail.json
+python bench.py --full > $O/bench_default.out 2> $O/bench_default.err; tail -1 $O/bench_default.out > $O/bench_default_final_line.json; cp bench_detail.json $O/bench_default_final_detail.json
 cat $O/gpu_tests_final.txt; wc -c $O/bench_default_final_line.json

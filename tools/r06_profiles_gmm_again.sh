@@ -17,5 +17,5 @@ python tools/make_traffic.py $R > $O/make_traffic.log 2>&1; cat $O/make_traffic.
 cp profiles/traffic_first_pass.json $O/traffic_first_pass.json; cp profiles/traffic_gmm_tile.json $O/traffic_gmm_tile.json
 bash tools/prof_run.sh ${R}_default --gpus 1 --steps 20 --warmup 5 > /dev/null 2>&1
 cp gpurun_out/prof_${R}_default/summary.json $O/default_command_kernel_trace_summary.json; cp gpurun_out/prof_${R}_default/bench_line.json $O/default_command_bench_line_under_rocprof.json
-python bench.py > $O/bench_default.out 2> $O/bench_default.err; tail -1 $O/bench_default.out > $O/bench_default_final_line.json; cp bench_detail.json $O/bench_default_final_detail.json
+python bench.py --full > $O/bench_default.out 2> $O/bench_default.err; tail -1 $O/bench_default.out > $O/bench_default_final_line.json; cp bench_detail.json $O/bench_default_final_detail.json
 wc -c $O/bench_default_final_line.json

@@ -29,7 +29,7 @@ def prepare(d: Path):
     import bench
     d.mkdir(parents=True, exist_ok=True)
     task, jargs, prefix = bench.build_reference_task(d, 20000, 800)
-    assert prefix is not None, "julius_amd/jamd_export missing"
+    assert prefix is not None, "oracle/_ref/bin/jamd_export missing"
     for u in range(32):
         np.save(d / f"utt{u}.npy", synth.make_utterance(task, nwords=30, seed=u)[0])
     rng = np.random.default_rng(7)
