@@ -541,14 +541,19 @@ int  jamd_beam_stream_push_dev(jamd_beam *b, const float *dev_scores, int nstate
  * beam.c:1342-1516, first-writer-wins propagation) with one lane per utterance, so that
  * the word trellis equals the reference's bit for bit even where exact score ties are
  * broken by visiting order.  Two to three orders of magnitude slower per utterance;
- * parallel only across the utterances of a batch.  Default is off (the frame-parallel
- * kernel, identical whenever jamd_pass1_result.ties == 0). */
+ * parallel only across the utterances of a batch.  on == 0 returns to the work area's
+ * default (jamd_beam_create()), from JAMD_ORDER_EXACT_SERIAL too: JAMD_ORDER_EXACT where the
+ * exact-order kernel serves the work area, else JAMD_ORDER_FAST.  A grammar with a forward
+ * DFA is the exception: the canonical-tie kernel cannot carry its state, so such a work area
+ * that the exact-order kernel cannot serve starts in strict order, and on == 0 is refused
+ * (JAMD_ESTATE; the mode stays strict).  Either direction returns JAMD_ESTATE while a
+ * streaming session is open. */
 int  jamd_beam_set_strict_order(jamd_beam *b, int on);
 /* How exact score ties are resolved (they are the only freedom a parallel schedule has; every
  * float is the reference's float in all modes):
  *   JAMD_ORDER_EXACT   (default; multipath lexicons included; beams up to about 12 000: up to ~950 the survivors live
  *       in LDS; wider beams keep them in the utterance's slice of HBM and the pruning step overlays the whole LDS
- *       image; the closed-form extraction serves beams up to 4 400, beyond that the heap's extraction loop itself
+ *       image; the closed-form extraction serves beams up to about 5 000, beyond that the heap's extraction loop itself
  *       runs pipelined on one wave):
  *       frame-parallel kernel with the reference's own semantics -- candidates keyed by their position
  *       in the reference's visiting order (first writer wins, propagate_token() beam.c:1945-1980,

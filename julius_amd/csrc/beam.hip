@@ -1937,6 +1937,15 @@ int jamd_beam_stream_push_dev(jamd_beam *b, const float *dev_scores, int nstate,
 
 int jamd_beam_set_strict_order(jamd_beam *b, int on) {
   if (!b) { jamd_set_error("jamd_beam_set_strict_order: NULL"); return JAMD_EINVAL; }
+  // (the parked state of an open session is the layout of the kernel that wrote it)
+  if (b->streaming > 0) { jamd_set_error("jamd_beam_set_strict_order: a streaming session is open"); return JAMD_ESTATE; }
+  if (!on && b->lex->d.nfwd > 0 && b->exact_status != 0) {
+    // the default of such a work area is strict order (jamd_beam_create()): the canonical-tie kernel would drop the
+    // forward DFA's state
+    jamd_set_error("jamd_beam_set_strict_order: a grammar with a forward DFA stays in strict order where the exact-order "
+                   "kernel cannot serve the work area (beam %d)", b->w.beam);
+    return JAMD_ESTATE;
+  }
   JAMD_HIP(hipSetDevice(b->eng->device));
   if (on && b->sw.token == nullptr) {
     const size_t U = (size_t)b->max_utts;
@@ -1950,7 +1959,10 @@ int jamd_beam_set_strict_order(jamd_beam *b, int on) {
     JAMD_HIP(hipMalloc(&p, U * b->w.nnode * sizeof(int))); b->owned.push_back(p); b->sw.token = (int *)p;
   }
   b->strict = on != 0;
-  if (!on) b->exact = b->exact_status == 0;          // back to the work area's default order (jamd_beam_create())
+  if (!on) {                                          // back to the work area's default order (jamd_beam_create())
+    b->exact = b->exact_status == 0;
+    b->xw.prune_mode = b->xw_half.prune_mode = 0;
+  }
   return JAMD_OK;
 }
 

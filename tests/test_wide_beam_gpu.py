@@ -112,8 +112,9 @@ def test_wide_beam_streaming_equals_one_shot(engine, ref, big_task, tmp_path):
 @pytest.mark.parametrize("mode", ["exact", "exact_serial"])
 @pytest.mark.parametrize("beam", [2000, 3000, 4000, 4400, 5000])
 def test_prune_order_wide(engine, oracle, beam, mode):
-    """The pruning step alone at wide beams (wide LDS layout; beam 5000: no room for the top lists) on score vectors
-    full of exact ties, against the sequential restatement of sort_token_no_order() (beam.c:1492)."""
+    """The pruning step alone at wide beams (wide LDS layout; beam 5000: near the end of the closed-form extraction, which
+    test_beam_limits_gpu.py straddles) on score vectors full of exact ties, against the sequential restatement of
+    sort_token_no_order() (beam.c:1492)."""
     from beamutil import load_beam_golden
     g = load_beam_golden("beam_rank.npz")
     lx = lib.Lexicon(engine, g["lex"])
