@@ -644,6 +644,85 @@ int  jamd_beam_results(jamd_beam *b, jamd_pass1_result *out, int nutt);
  * 218-267,468-477) is (endtime, wid). */
 int  jamd_beam_trellis(jamd_beam *b, int utt, jamd_trellis_atom *atoms, int cap, int *natom);
 
+/* ---- audio front end: PCM samples -> MFCC / FBANK / MELSPEC features ------------------------
+ * The reference's buffered (non-realtime) front end, the one `julius -input rawfile` runs:
+ * Wav2MFCC() (libsent/src/wav2mfcc/wav2mfcc-buffer.c) with WMP_calc() and the tables of
+ * mfcc-core.c (MFCC_SINCOS_TABLE on), then the splicing of libjulius/src/wav2mfcc.c:162-169.
+ * Bit-identical to it.  The descriptor carries the fields of Value (libsent/include/sent/mfcc.h:
+ * 76-115), the static CMN/CVN vectors of CMNWork (-cmnload FILE -cmnstatic) and the splice count.
+ * paramtype is an HTK parameter kind code: base JAMD_F_MFCC / _FBANK / _MELSPEC ORed with the
+ * qualifier bits below (htk_defs.h:57-66); vecsize the vector size the acoustic model declares.
+ *
+ * NOT SERVED -- jamd_frontend_create() returns JAMD_EINVAL and says why (there is no host front end
+ * behind this library):
+ *   - spectral subtraction (-sscalc, -ssload): ss != 0;
+ *   - realtime input and MAP-CMN (the pipelined front end of wav2mfcc-pipe.c): realtime != 0;
+ *   - kinds other than MFCC, FBANK and MELSPEC, FBANK / MELSPEC with _E or _0 (WMP_calc() leaves
+ *     those slots unwritten), _N without _E and _D, _A without _D. */
+#define JAMD_F_MFCC     6
+#define JAMD_F_FBANK    7
+#define JAMD_F_MELSPEC  8
+#define JAMD_F_E        0x0040
+#define JAMD_F_N        0x0080
+#define JAMD_F_D        0x0100
+#define JAMD_F_A        0x0200
+#define JAMD_F_Z        0x0800
+#define JAMD_F_0        0x2000
+
+typedef struct {
+  int paramtype, vecsize;             /* kind and model vector size the derived fields come from         */
+  int smp_period, smp_freq;           /* 100 ns units / Hz                                                */
+  int framesize, frameshift;          /* samples                                                          */
+  float preEmph;
+  int lifter, fbank_num, delWin, accWin;
+  float silFloor, escale;
+  int hipass, lopass;                 /* Hz, -1 = off                                                     */
+  int enormal, raw_e, zmeanframe, usepower, cvn;
+  float vtln_alpha, vtln_upper, vtln_lower;
+  /* derived by calc_para_from_header() (para.c:323-372) */
+  int basetype, delta, acc, energy, c0, absesup, cmn, mfcc_dim, baselen, vecbuflen, veclen;
+  /* -cmnload: static mean [veclen] (the first mfcc_dim + c0 entries are read) and variance [veclen];
+   * NULL = computed over each utterance.  static_cvn_only = CMNWork.static_cvn_only. */
+  const float *cmean_init;
+  const float *cvar_init;
+  int static_cvn_only;
+  int splice;                         /* -splice N (1 = none)                                             */
+  int ss, realtime;                   /* refused: spectral subtraction / realtime or MAP-CMN             */
+} jamd_frontend_desc;
+
+typedef struct jamd_frontend jamd_frontend;
+/* make_default_para() (para.c:86-107) then calc_para_from_header(paramtype, vecsize); splice 1. */
+int  jamd_frontend_default_desc(int paramtype, int vecsize, jamd_frontend_desc *d);
+/* calc_para_from_header() alone (the kind fields, and fbank_num for FBANK / MELSPEC). */
+int  jamd_frontend_set_kind(jamd_frontend_desc *d, int paramtype, int vecsize);
+/* htk_config_file_parse() (para.c:196-321) over d in place.  Keys the reference does not take are
+ * refused (JAMD_EINVAL naming the key); TARGETKIND and NUMCEPS are skipped as there. */
+int  jamd_frontend_htkconf(const char *path, jamd_frontend_desc *d);
+/* Host only: a table the front end is built from, as WMP_work_new() makes it.  name: "hamming",
+ * "fft_cos", "fft_sin", "dct", "wcep", "twiddle_re", "twiddle_im" (double), "cf", "lowt" (float,
+ * [maxChan + 1] / [fftN/2 + 1]), "lochan" (short, [fftN/2 + 1]), "info" (int: fftN, n, klo, khi),
+ * "scalars" (float: fres, sqrt2var).  Returns the element count (copies min(count, cap)). */
+int  jamd_frontend_table(const jamd_frontend_desc *d, const char *name, void *out, int cap);
+int  jamd_frontend_create(jamd_engine *e, const jamd_frontend_desc *d, jamd_frontend **out);
+void jamd_frontend_destroy(jamd_frontend *f);
+int  jamd_frontend_veclen(const jamd_frontend *f);             /* veclen * splice: floats per output frame */
+/* Output frames of one utterance of nsamples samples: (n - framesize)/frameshift + 1 - (splice - 1),
+ * <= 0 when the input is too short (also when n < framesize). */
+int  jamd_frontend_frames(const jamd_frontend_desc *d, int64_t nsamples);
+/* nutt utterances back to back in dev_samples (int16), utterance u = samples [sample_off[u],
+ * sample_off[u+1]) (host array).  Writes the features of all utterances back to back into dev_out
+ * ([sum frames][veclen * splice], the layout jamd_gmm_outprob_utts_dev / jamd_dnn_outprob_dev /
+ * jamd_beam_pass1_dev take) and, if frame_off is not NULL, the host frame offsets [nutt + 1].
+ * An utterance too short for one output frame: JAMD_EINVAL, nothing written.
+ * The object's device scratch (per-frame statics, the vectors before normalisation, the CMN / MVN statistics, the
+ * offsets) is reused by every call: calls on one object must not be in flight on two streams at once -- queue them on
+ * one stream (they are then ordered), or use one object per stream.  Windows of up to 4096 samples are served (fftN
+ * up to 4096; the frame kernel takes two frames per workgroup instead of four at fftN 4096). */
+int  jamd_frontend_run_dev(jamd_frontend *f, const int16_t *dev_samples, const int64_t *sample_off, int nutt,
+                           float *dev_out, int *frame_off, void *stream);
+int  jamd_frontend_run_host(jamd_frontend *f, const int16_t *samples, const int64_t *sample_off, int nutt,
+                            float *out, int *frame_off);
+
 #ifdef __cplusplus
 }
 #endif

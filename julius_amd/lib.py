@@ -44,6 +44,19 @@ class DnnDesc(C.Structure):
     ]
 
 
+class FrontendDesc(C.Structure):
+    """jamd_frontend_desc (include/julius_amd.h): the reference's Value plus static CMN / splice."""
+    _fields_ = [(n, C.c_int) for n in ("paramtype", "vecsize", "smp_period", "smp_freq", "framesize", "frameshift")] + [
+        ("preEmph", C.c_float)] + [(n, C.c_int) for n in ("lifter", "fbank_num", "delWin", "accWin")] + [
+        ("silFloor", C.c_float), ("escale", C.c_float)] + [
+        (n, C.c_int) for n in ("hipass", "lopass", "enormal", "raw_e", "zmeanframe", "usepower", "cvn")] + [
+        (n, C.c_float) for n in ("vtln_alpha", "vtln_upper", "vtln_lower")] + [
+        (n, C.c_int) for n in ("basetype", "delta", "acc", "energy", "c0", "absesup", "cmn", "mfcc_dim", "baselen",
+                               "vecbuflen", "veclen")] + [
+        ("cmean_init", C.c_void_p), ("cvar_init", C.c_void_p), ("static_cvn_only", C.c_int), ("splice", C.c_int),
+        ("ss", C.c_int), ("realtime", C.c_int)]
+
+
 _lib = None
 
 
@@ -148,6 +161,16 @@ def load():
         "jamd_beam_stream_begin": (ci, [vp, ci]),
         "jamd_beam_stream_push_dev": (ci, [vp, vp, ci, vp, ci, ci, vp]),
         "jamd_beam_trellis": (ci, [vp, ci, vp, ci, P(ci)]),
+        "jamd_frontend_default_desc": (ci, [ci, ci, P(FrontendDesc)]),
+        "jamd_frontend_set_kind": (ci, [P(FrontendDesc), ci, ci]),
+        "jamd_frontend_htkconf": (ci, [C.c_char_p, P(FrontendDesc)]),
+        "jamd_frontend_table": (ci, [P(FrontendDesc), C.c_char_p, vp, ci]),
+        "jamd_frontend_create": (ci, [vp, P(FrontendDesc), P(vp)]),
+        "jamd_frontend_destroy": (None, [vp]),
+        "jamd_frontend_veclen": (ci, [vp]),
+        "jamd_frontend_frames": (ci, [P(FrontendDesc), C.c_int64]),
+        "jamd_frontend_run_dev": (ci, [vp, vp, vp, ci, vp, vp, vp]),
+        "jamd_frontend_run_host": (ci, [vp, vp, vp, ci, vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -751,6 +774,98 @@ class Beam:
     def close(self):
         if getattr(self, "h", None):
             load().jamd_beam_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+F_BASE = {"MFCC": 6, "FBANK": 7, "MELSPEC": 8}
+F_QUAL = {"E": 0x40, "N": 0x80, "D": 0x100, "A": 0x200, "Z": 0x800, "0": 0x2000}
+
+
+def param_kind(name: str) -> int:
+    """HTK parameter kind name ("MFCC_E_D_N_Z") -> code, as param_str2code() (libsent/src/anlz/paramtypes.c)."""
+    base, *quals = name.upper().split("_")
+    if base not in F_BASE or any(q not in F_QUAL for q in quals):
+        raise JamdError(f"parameter kind {name!r}: base MFCC / FBANK / MELSPEC with _E _N _D _A _Z _0 only")
+    code = F_BASE[base]
+    for q in quals:
+        code |= F_QUAL[q]
+    return code
+
+
+class Frontend:
+    """Audio front end (jamd_frontend): Wav2MFCC() of libsent/src/wav2mfcc/wav2mfcc-buffer.c plus the
+    splicing of libjulius/src/wav2mfcc.c, on the device.  int16 PCM in, features [T][veclen * splice] out."""
+
+    def __init__(self, eng: Engine, desc: FrontendDesc, cmean=None, cvar=None):
+        self.eng, self.desc = eng, desc
+        self._cm = _f32(cmean) if cmean is not None else None
+        self._cv = _f32(cvar) if cvar is not None else None
+        desc.cmean_init = self._cm.ctypes.data if self._cm is not None else None
+        desc.cvar_init = self._cv.ctypes.data if self._cv is not None else None
+        h = C.c_void_p()
+        _check(load().jamd_frontend_create(eng.h, C.byref(desc), C.byref(h)), "jamd_frontend_create")
+        self.h = h
+        self.veclen = load().jamd_frontend_veclen(h)
+
+    @staticmethod
+    def desc_for(kind, vecsize: int, htkconf=None, **fields) -> FrontendDesc:
+        """make_default_para() + calc_para_from_header(kind, vecsize), an optional HTK config file on top
+        (then the kind again, as the AM header is applied after the config), then `fields` verbatim."""
+        code = param_kind(kind) if isinstance(kind, str) else int(kind)
+        d = FrontendDesc()
+        _check(load().jamd_frontend_default_desc(code, int(vecsize), C.byref(d)), "jamd_frontend_default_desc")
+        if htkconf is not None:
+            _check(load().jamd_frontend_htkconf(str(htkconf).encode(), C.byref(d)), "jamd_frontend_htkconf")
+            _check(load().jamd_frontend_set_kind(C.byref(d), code, int(vecsize)), "jamd_frontend_set_kind")
+        for k, v in fields.items():
+            setattr(d, k, v)
+        return d
+
+    @classmethod
+    def from_kind(cls, eng: Engine, kind, vecsize: int, cmean=None, cvar=None, **fields):
+        return cls(eng, cls.desc_for(kind, vecsize, **fields), cmean, cvar)
+
+    @classmethod
+    def from_htkconf(cls, eng: Engine, path, kind, vecsize: int, cmean=None, cvar=None, **fields):
+        return cls(eng, cls.desc_for(kind, vecsize, htkconf=path, **fields), cmean, cvar)
+
+    def frames(self, nsamples: int) -> int:
+        return load().jamd_frontend_frames(C.byref(self.desc), int(nsamples))
+
+    @staticmethod
+    def _pack(utts):
+        utts = [np.ascontiguousarray(u, dtype=np.int16) for u in utts]
+        off = np.zeros(len(utts) + 1, np.int64)
+        off[1:] = np.cumsum([len(u) for u in utts])
+        return (np.concatenate(utts) if utts else np.zeros(0, np.int16)), off
+
+    def run_host(self, utts):
+        """list of int16 arrays -> (features [sum T][veclen * splice] float32, frame_off [nutt + 1] int32)."""
+        samples, off = self._pack(utts)
+        T = sum(self.frames(off[u + 1] - off[u]) for u in range(len(utts)))
+        out = np.zeros((max(T, 0), self.veclen), np.float32)
+        foff = np.zeros(len(utts) + 1, np.int32)
+        _check(load().jamd_frontend_run_host(self.h, samples.ctypes.data, off.ctypes.data, len(utts),
+                                             out.ctypes.data, foff.ctypes.data), "jamd_frontend_run_host")
+        return out, foff
+
+    def run_dev(self, dev_samples: int, sample_off, dev_out: int, stream: int = 0):
+        """Device samples and features; sample_off host int64 [nutt + 1].  Returns frame_off [nutt + 1]."""
+        off = np.ascontiguousarray(sample_off, dtype=np.int64)
+        foff = np.zeros(len(off), np.int32)
+        _check(load().jamd_frontend_run_dev(self.h, dev_samples, off.ctypes.data, len(off) - 1, dev_out,
+                                            foff.ctypes.data, stream or None), "jamd_frontend_run_dev")
+        return foff
+
+    def close(self):
+        if getattr(self, "h", None):
+            load().jamd_frontend_destroy(self.h)
             self.h = None
 
     def __del__(self):

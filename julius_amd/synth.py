@@ -1107,3 +1107,32 @@ def make_forward_grammar_utterance(g, seed=0, frames_per_state=3, noise=0.7, nwo
     st = np.repeat(np.array(seq), frames_per_state)
     fr = model["centre"][st] + rng.normal(0, noise, size=(len(st), model["mean"].shape[1]))
     return fr.astype(np.float32), [g["words"][i][0] for i in ids]
+
+
+def make_audio(nsamples, seed=0, sfreq=16000, dc=None, zero_runs=2, silent_frac=0.15, clip=True):
+    """Seeded synthetic 16-bit PCM for the front end: harmonic chirps with a moving pitch plus noise,
+    quiet stretches, runs of exact zeros (what the reference's zero stripping removes), a DC offset and
+    samples clipped to +32767 / -32768.  Returns int16 [nsamples]."""
+    rng = np.random.default_rng(seed)
+    n = int(nsamples)
+    t = np.arange(n) / float(sfreq)
+    f0 = rng.uniform(90, 250) * (1.0 + 0.3 * np.sin(2 * np.pi * rng.uniform(0.2, 1.5) * t + rng.uniform(0, 6.3)))
+    phase = 2 * np.pi * np.cumsum(f0) / sfreq
+    x = np.zeros(n)
+    for h in range(1, 12):
+        x += rng.uniform(0.2, 1.0) / h * np.sin(h * phase + rng.uniform(0, 6.3))
+    env = 0.5 + 0.5 * np.sin(2 * np.pi * rng.uniform(0.5, 3.0) * t + rng.uniform(0, 6.3))
+    x = x * env * rng.uniform(2000, 9000) + rng.normal(0, rng.uniform(20, 400), n)
+    x += rng.uniform(-300, 300) if dc is None else dc
+    if n > 100 and silent_frac > 0:            # quiet stretches: low noise only
+        for _ in range(rng.integers(1, 4)):
+            a = int(rng.integers(0, n)); b = min(n, a + int(n * silent_frac * rng.uniform(0.3, 1.0)))
+            x[a:b] = rng.normal(0, 3, b - a)
+    if clip and n > 10:                        # overdriven stretch: clipped at both rails
+        a = int(rng.integers(0, n)); b = min(n, a + int(rng.integers(1, max(2, n // 20))))
+        x[a:b] *= 8.0
+    y = np.clip(np.round(x), -32768, 32767).astype(np.int16)
+    for _ in range(zero_runs if n > 100 else 0):   # runs of exact zeros
+        a = int(rng.integers(0, n)); b = min(n, a + int(rng.integers(1, 600)))
+        y[a:b] = 0
+    return y

@@ -1,0 +1,95 @@
+"""Device audio front end (jamd_frontend_run_dev) on the C3 batch shape -- 512 ragged utterances, 727 200
+frames at 16 kHz / 10 ms -- beside the compiled reference's Wav2MFCC() on one host core of the same machine.
+
+  python tools/frontend_timing.py [--reps 10] [--ref-frames 30000] [--json out.json]
+
+Device time: wall clock of run_dev + stream sync (median of --reps, after a warm-up), samples already on the
+device.  Reference: the Wav2MFCC() call alone of oracle/_ref/libjref.so over utterances of the same length distribution
+(--ref-frames frames in all), per frame, scaled to the batch.  Both kinds of the issue: MFCC_E_D_A_Z (39) and
+MFCC_E_D_N_Z (25)."""
+import argparse
+import json
+import sys
+import time
+from pathlib import Path
+
+import numpy as np
+
+ROOT = Path(__file__).resolve().parent.parent
+sys.path[:0] = [str(ROOT), str(ROOT / "tests")]
+
+from julius_amd import lib, synth  # noqa: E402
+
+NUTT, FRAMES = 512, 727200
+
+
+def batch(seed=0):
+    """512 utterances, 727 200 frames in all, lengths spread 0.5x .. 1.5x the mean, cut from synthetic speech."""
+    rng = np.random.default_rng(seed)
+    w = rng.uniform(0.5, 1.5, NUTT)
+    T = np.floor(w / w.sum() * FRAMES).astype(np.int64)
+    T[: FRAMES - T.sum()] += 1
+    src = synth.make_audio(16000 * 120, seed=seed + 1)
+    utts = []
+    for t in T:
+        n = 400 + 160 * (int(t) - 1)
+        reps = -(-n // len(src))
+        a = int(rng.integers(0, len(src)))
+        utts.append(np.roll(np.tile(src, reps), -a)[:n])
+    return utts
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=10)
+    ap.add_argument("--ref-frames", type=int, default=30000)
+    ap.add_argument("--json")
+    a = ap.parse_args()
+    eng = lib.Engine(0)
+    utts = batch()
+    samples, off = lib.Frontend._pack(utts)
+    d_in = lib.DevBuf(eng, samples.nbytes).upload(samples)
+    out = {"utterances": NUTT, "frames": FRAMES, "samples": int(off[-1]), "kinds": {}}
+    for kind, vs in (("MFCC_E_D_A_Z", 39), ("MFCC_E_D_N_Z", 25)):
+        fe = lib.Frontend.from_kind(eng, kind, vs)
+        d_out = lib.DevBuf(eng, 4 * FRAMES * fe.veclen)
+        foff = fe.run_dev(d_in.ptr, off, d_out.ptr)
+        eng.sync()
+        assert foff[-1] == FRAMES, foff[-1]
+        ts = []
+        for _ in range(a.reps):
+            t0 = time.perf_counter()
+            fe.run_dev(d_in.ptr, off, d_out.ptr)
+            eng.sync()
+            ts.append(time.perf_counter() - t0)
+        dev_ms = 1e3 * float(np.median(ts))
+        rec = {"device_ms_per_batch": round(dev_ms, 3), "device_ms_min": round(1e3 * min(ts), 3),
+               "device_rtf_inv": round(FRAMES * 0.01 / (dev_ms / 1e3), 1)}
+        try:
+            from oracle import pyoracle
+            from frontendref import RefFrontend
+            rf = RefFrontend(pyoracle.Ref())
+            v = rf.para(lib.param_kind(kind), vs)
+            nref, tref, k = 0, 0.0, 0
+            while nref < a.ref_frames:
+                f = rf.wav2mfcc(utts[k], v)
+                tref += rf.last_s
+                nref += len(f)
+                k += 1
+            us = 1e6 * tref / nref
+            rec.update(ref_us_per_frame_1core=round(us, 3), ref_rtf_inv_1core=round(1e4 / us, 1),
+                       ref_ms_per_batch_1core=round(us * FRAMES / 1e3, 1),
+                       ref_ms_per_batch_16core_ideal=round(us * FRAMES / 1e3 / 16, 1),
+                       speedup_vs_1core=round(us * FRAMES / 1e3 / dev_ms, 1))
+        except FileNotFoundError as e:
+            rec["ref"] = f"not measured: {e}"
+        out["kinds"][kind] = rec
+        fe.close()
+    line = json.dumps({"frontend_timing": out})
+    print(line)
+    if a.json:
+        Path(a.json).write_text(line + "\n")
+
+
+if __name__ == "__main__":
+    main()
