@@ -206,18 +206,48 @@ def write_hmmdefs(path, model, phones=None, trans=None, kind="MFCC_E_D_A", state
 
 
 # ------------------------------------------------------------------------ DNN
-def make_dnn(dims=(528, 2048, 2048, 2048, 2048, 2048, 2048, 4000), seed=0):
+def make_dnn(dims=(528, 2048, 2048, 2048, 2048, 2048, 2048, 4000), seed=0, gain=1.0, out_gain=1.0):
     """Random-init DNN of the ENVR-v5.4 shape (BASELINE.json configs[3]):
     W[l] ~ N(0, 1/sqrt(in)) stored [out][in], b ~ N(0, 0.1), Dirichlet prior
-    stored as log10 (state_prior_log10nize, calc_dnn.c:699-703)."""
+    stored as log10 (state_prior_log10nize, calc_dnn.c:699-703).
+    `gain` multiplies the hidden layers' weights (large: units saturate past the logistic's +-8 clamp), `out_gain`
+    the output layer's (large: peaked rows, terms below the log-sum's cut-off).  At 1.0 the multiplication is
+    skipped, so the arrays are byte for byte those of the two-argument form."""
     rng = np.random.default_rng(seed)
     w, b = [], []
-    for l in range(len(dims) - 1):
-        w.append((rng.standard_normal((dims[l + 1], dims[l])) / np.sqrt(dims[l])).astype(np.float32))
+    nl = len(dims) - 1
+    for l in range(nl):
+        wl = (rng.standard_normal((dims[l + 1], dims[l])) / np.sqrt(dims[l])).astype(np.float32)
+        g = out_gain if l == nl - 1 else gain
+        if g != 1.0:
+            wl = (wl * np.float32(g)).astype(np.float32)
+        w.append(wl)
         b.append((0.1 * rng.standard_normal(dims[l + 1])).astype(np.float32))
     p = rng.dirichlet(np.full(dims[-1], 5.0)).astype(np.float32)
     prior = np.log10(p.astype(np.float64)).astype(np.float32)
     return dict(dims=np.asarray(dims, dtype=np.int32), w=w, b=b, prior=prior, prior_lin=p)
+
+
+def make_probe_dnn(S=8, hidden=True, scales=None, prior=None):
+    """A network whose pre-activations are known exactly, for the edges of the logistic and of the output log-sum.
+    8 inputs; a hidden probe has dims (8, 8, S): an identity hidden layer with zero bias, then the output layer; an
+    output probe has dims (8, S).  Output row i is scales[i] * e_(i mod 8) with zero bias (scales defaults to ones,
+    prior to zeros).  Each of the eight fused chains of a unit then holds one product and the other seven are zero,
+    so the pre-activation of hidden unit i is x_i, and of output i scales[i] * (its input i mod 8), bit for bit
+    when the scale is a power of two -- except that -0.0 becomes +0.0 in the sum of the lanes (-0 + +0 = +0).
+    `prior` is the log10 prior; prior_lin = 10 ** prior is consistent with it only as far as float32 goes."""
+    S = int(S)
+    scales = np.ones(S, np.float32) if scales is None else np.asarray(scales, dtype=np.float32)
+    assert scales.shape == (S,)
+    wo = np.zeros((S, 8), np.float32)
+    wo[np.arange(S), np.arange(S) % 8] = scales
+    w, b, dims = [wo], [np.zeros(S, np.float32)], [8, S]
+    if hidden:
+        w.insert(0, np.eye(8, dtype=np.float32)); b.insert(0, np.zeros(8, np.float32)); dims.insert(1, 8)
+    prior = np.zeros(S, np.float32) if prior is None else np.asarray(prior, dtype=np.float32)
+    assert prior.shape == (S,)
+    return dict(dims=np.asarray(dims, dtype=np.int32), w=w, b=b, prior=prior,
+                prior_lin=(10.0 ** prior.astype(np.float64)).astype(np.float32))
 
 
 def _dnn_hidden(dnn, x):
