@@ -608,7 +608,7 @@ int  jamd_beam_wait_started(jamd_beam *b);
 int  jamd_beam_stream_wait_resident(jamd_beam *b, void *stream);
 /* Test entry: sets the resident counter (the device word the first-pass workgroups bump, and the host's bookkeeping of
  * it) to `count`, as if that many workgroups had been launched since the work area was created.  The counter is 32 bits
- * wide and drained back to zero before it could wrap (csrc/beam.hip mark_started()); a test starts it just below that
+ * wide and drained back to zero before it could wrap (csrc/beam_api.hip mark_started()); a test starts it just below that
  * point instead of launching 2^31 workgroups.  The device is synchronised first. */
 int  jamd_beam_debug_preset_resident(jamd_beam *b, unsigned count);
 /* Test entry: workgroups accounted since the last drain (*launched) and the value the next

@@ -1,6 +1,7 @@
-// beam_common.h -- declarations shared by the first-pass kernels (beam.hip: frame-parallel and strict-order
-// kernels, host side; beam_exact.hip: the exact-order frame-parallel kernel).  Everything lives in an
-// named namespace (the structs cross translation units), the functions are inline.
+// beam_common.h -- declarations shared by the first-pass kernels (beam.hip: the frame-parallel canonical-tie kernel;
+// beam_strict.hip: the strict-order kernel; beam_exact.hip: the exact-order frame-parallel kernel) and their host side
+// (beam_lexicon.hip, beam_api.hip).  Everything lives in a named namespace (the structs cross translation units), the
+// functions are inline.
 #pragma once
 #include "jamd_device.h"
 #include <type_traits>

@@ -1,4 +1,4 @@
-// beam_exact.h -- interface between beam.hip (host side of the first pass) and beam_exact.hip (the
+// beam_exact.h -- interface between beam_api.hip (host side of the first pass) and beam_exact.hip (the
 // exact-order frame-parallel kernel).  Internal, not installed.
 #pragma once
 #include "beam_common.h"

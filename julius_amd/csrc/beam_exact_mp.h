@@ -3,7 +3,7 @@
 // (cells, creation-order bitmap, heaps, exact_prune()) and the slice macros are that file's.
 //
 // The reference runs a different frame for such models (beam.c:2747-2836, :2930-2943, :3066-3073; the frame as
-// decoded one lane per utterance by beam_strict_mp_kernel, beam.hip):
+// decoded one lane per utterance by beam_strict_kernel<true>, beam_strict.hip):
 //   1  word-internal transitions of every survivor                               (steps 0', A', C1: tokens WITHOUT this
 //                                                                                  frame's output probability)
 //   2  sort_token_no_order() over the NEW tokens                                  (step M)

@@ -1,4 +1,4 @@
-"""GPU: the HIP first pass (beam.hip, through the C ABI) against the golden
+"""GPU: the HIP first pass (csrc/beam*.hip, through the C ABI) against the golden
 fixtures of the compiled reference, the oracle, and -- when oracle/_ref is
 present -- the reference recogniser itself.  Bit-exact trellis: word ids,
 begin/end frames, predecessor links and float scores.  (jamd_pass1_result.ties
@@ -429,7 +429,7 @@ def test_wordlist_vs_reference_live(engine, oracle, ref, tmp_path, triphone, mod
 
 
 # ---- multipath lexicons ------------------------------------------------------------------------------
-# beam_strict_mp_kernel (strict-order only): first hardware run at the start of round 2
+# beam_strict_kernel<true> (csrc/beam_strict.hip; strict-order only): first hardware run at the start of round 2
 # (profiles/r02a_pending_multipath_tests.txt); the CPU restatement of the same frame loop is pinned to the
 # reference in tests/test_beam_oracle.py.
 

@@ -36,8 +36,8 @@ def _last_true(pred, lo, hi):
 
 
 def fast_lds_image(beam, nstate, tok_bytes=32):
-    """The canonical-tie kernel's LDS image for a beam, restating jamd_beam_create() (csrc/beam.hip:1679-1700) and the
-    score-row test of jamd_beam_pass1_dev() (:1858): (survivors in LDS, cell-table slots, score row cached)."""
+    """The canonical-tie kernel's LDS image for a beam, restating fbeam_layout() and the score-row test of
+    fbeam_launch() (csrc/beam.hip): (survivors in LDS, cell-table slots, score row cached)."""
     max_dyn, hist = 159 * 1024, 2048 * 4            # kMaxDynLds, kHistBytes (csrc/beam_common.h)
     hsize = 64
     while hsize < 2 * beam:

@@ -1,4 +1,4 @@
-"""GPU: the bookkeeping of the resident counter (csrc/beam.hip mark_started() / account_launch()) -- the device word the
+"""GPU: the bookkeeping of the resident counter (csrc/beam_api.hip mark_started() / account_launch()) -- the device word the
 first-pass workgroups bump when they start, on which the scoring stream of a pipelining host waits
 (jamd_beam_stream_wait_resident(): hipStreamWaitValue32, no host involvement).  Two fixes of round 5 that had
 no test: the counter is drained back to zero before its 32 bits could wrap, and a REFUSED launch

@@ -1,12 +1,14 @@
 #!/usr/bin/env python3
 """Register / spill / scratch / LDS figures of every kernel in a gfx950 code object (the AMDGPU metadata note).
 
-  python tools/kernel_regs.py [julius_amd/libjulius_amd.so | file.o] [--filter beam_exact] [--json out.json]
+  python tools/kernel_regs.py [julius_amd/libjulius_amd.so | file.o] [--filter beam_exact] [--json out.json] [--diff OTHER]
 
 Unbundles the gfx950 code object (clang-offload-bundler for .o files, the .hip_fatbin section for the shared library)
 and prints, per kernel: VGPRs, AGPRs, SGPRs, SGPR spills, VGPR spills, scratch bytes per thread, static LDS bytes, instruction
-count (llvm-objdump)."""
+count (llvm-objdump).  --diff OTHER compares against a second library kernel by kernel: those figures and the
+instruction text (addresses and encodings stripped); it lists what differs and exits 1 if anything does."""
 import argparse
+import hashlib
 import json
 import re
 import subprocess
@@ -57,11 +59,12 @@ def kernels_of(co: Path):
         m = re.match(r"^[0-9a-f]+ <(.+)>:$", line)
         if m:
             name = m.group(1)
-            counts[name] = {"insts": 0, "readlane": 0, "writelane": 0, "scratch": 0, "flat": 0}
+            counts[name] = {"insts": 0, "readlane": 0, "writelane": 0, "scratch": 0, "flat": 0, "text": hashlib.sha1()}
             continue
         if name and re.match(r"^\s+[a-z_0-9]+", line):
             c = counts[name]
             c["insts"] += 1
+            c["text"].update((" ".join(line.split("//")[0].split()) + "\n").encode())   # mnemonic + operands only
             op = line.split()[0]
             if op.startswith("v_readlane"):
                 c["readlane"] += 1
@@ -71,6 +74,8 @@ def kernels_of(co: Path):
                 c["scratch"] += 1
             elif op.startswith("flat_"):
                 c["flat"] += 1
+    for c in counts.values():
+        c["text"] = c["text"].hexdigest()
     out = []
     for r in recs:
         if ".sgpr_count" not in r:
@@ -97,16 +102,42 @@ def kernels_of(co: Path):
     return out
 
 
+def load(path):
+    with tempfile.TemporaryDirectory() as td:
+        ks = []
+        for co in code_objects(Path(path), Path(td)):
+            ks += kernels_of(co)
+    return ks
+
+
+def diff(ks, other, flt):
+    """0 when every kernel (of those whose name contains `flt`) has the same figures and instruction text in both."""
+    a, b = ({k["name"]: k for k in x if not flt or flt in k["name"]} for x in (ks, other))
+    cols = ["vgpr", "agpr", "sgpr", "sgpr_spill", "vgpr_spill", "scratch_bytes", "lds_static", "insts", "text"]
+    bad = 0
+    for n in sorted(set(a) | set(b)):
+        if n not in a or n not in b:
+            print(f"only in {'this' if n in a else 'OTHER'}: {n}")
+            bad += 1
+            continue
+        d = [c for c in cols if a[n].get(c) != b[n].get(c)]
+        if d:
+            print(f"differs: {n}: " + ", ".join(f"{c} {a[n].get(c)} vs {b[n].get(c)}" for c in d))
+            bad += 1
+    print(f"{len(set(a) & set(b)) - sum(1 for n in set(a) & set(b) if any(a[n].get(c) != b[n].get(c) for c in cols))} kernels identical, {bad} differ or are unmatched")
+    return 1 if bad else 0
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("path", nargs="?", default=str(Path(__file__).resolve().parent.parent / "julius_amd" / "libjulius_amd.so"))
     ap.add_argument("--filter", default=None)
     ap.add_argument("--json", default=None)
+    ap.add_argument("--diff", default=None, metavar="OTHER")
     a = ap.parse_args()
-    with tempfile.TemporaryDirectory() as td:
-        ks = []
-        for co in code_objects(Path(a.path), Path(td)):
-            ks += kernels_of(co)
+    ks = load(a.path)
+    if a.diff:
+        return diff(ks, load(a.diff), a.filter)
     if a.filter:
         ks = [k for k in ks if a.filter in k["name"]]
     ks.sort(key=lambda k: k["name"])
