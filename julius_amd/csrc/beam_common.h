@@ -1,5 +1,5 @@
 // beam_common.h -- declarations shared by the first-pass kernels (beam.hip: the frame-parallel canonical-tie kernel;
-// beam_strict.hip: the strict-order kernel; beam_exact.hip: the exact-order frame-parallel kernel) and their host side
+// beam_strict.hip: the strict-order kernel; beam_exact.hip: the exact-order frame-parallel kernels) and their host side
 // (beam_lexicon.hip, beam_api.hip).  Everything lives in a named namespace (the structs cross translation units), the
 // functions are inline.
 #pragma once

@@ -1,9 +1,15 @@
-// beam_exact.h -- interface between beam_api.hip (host side of the first pass) and beam_exact.hip (the
-// exact-order frame-parallel kernel).  Internal, not installed.
+// beam_exact.h -- interface between beam_api.hip (host side of the first pass) and the exact-order frame-parallel
+// kernels: the layout of their LDS image (beam_exact_layout.hip) and their launches (beam_exact.hip).  Internal, not
+// installed.
 #pragma once
 #include "beam_common.h"
 
 namespace jamdb {
+
+// sizes the pruning step's layout and its device code (beam_prune.h) agree on
+constexpr int kMaxL = 20;                // heap positions < 2^21
+constexpr int kMaxCand = 64;             // tail candidates replayed with the parallel scheme; more fall back to the serial loop
+constexpr int kTakers = kMaxL + 2;       // occupants of one root-to-leaf chain
 
 struct XWork {
   Work w;                      // the slices of the frame-parallel kernel are reused as they are

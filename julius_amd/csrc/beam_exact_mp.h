@@ -1,6 +1,6 @@
-// beam_exact_mp.h -- multipath lexicons (hmminfo->multipath) on the exact-order frame-parallel machinery.
-// Included by beam_exact.hip inside its anonymous namespace, behind the kernel for ordinary lexicons: the helpers
-// (cells, creation-order bitmap, heaps, exact_prune()) and the slice macros are that file's.
+// beam_exact_mp.h -- multipath lexicons (hmminfo->multipath) on the exact-order frame-parallel machinery (K6m).
+// Included by beam_exact.hip behind its own kernel; self-sufficient: the pruning step and, through it, everything the
+// two frame kernels share (cells, scans, slice macros, views, entry and end of the kernel) come from beam_prune.h.
 //
 // The reference runs a different frame for such models (beam.c:2747-2836, :2930-2943, :3066-3073; the frame as
 // decoded one lane per utterance by beam_strict_kernel<true>, beam_strict.hip):
@@ -39,133 +39,35 @@
 // loop of step 3 has yet to visit -- or has visited already -- and the outcome depends on the loop's position; such
 // lexicons stay on the strict-order kernel.  (The reference builds none: wchmm_add_word() refuses a word whose models can
 // all be skipped, wchmm.c:1345-1362 -- only a hand-written descriptor gets here.)
+#pragma once
+#include "beam_prune.h"
 
-// sort_token_no_order() (beam.c:1492 over :1342-1480) carried out literally on (score bits << 32 | index) entries:
-// H[1..n] ends as tindex[0..n-1].  The heap in LDS when it fits (pipelined extraction), else in the slice (one lane).
-template <int NT>
-__device__ __forceinline__ void literal_sort(const unsigned *keys, int n, int k, lds_u64 *Hl, int heap_cap, unsigned long long *Hg) {
-  const int tid = tid_now();
-  const bool upward = k < n - k;
-  auto run = [&](auto Hh) -> void {
-    constexpr bool kLds = std::is_same<decltype(Hh), lds_u64 *>::value;
-    for (int i = tid; i < n; i += NT) Hh[i + 1] = ((unsigned long long)keys[i] << 32) | (unsigned)i;
-    if (tid == 0) Hh[0] = 0ull;
-    __syncthreads();
-    bool heaped = false;
-    if constexpr (kLds) heaped = upward ? heapify_overlapped<true, NT>(Hh, n) : heapify_overlapped<false, NT>(Hh, n);
-    if (!heaped) { if (upward) heapify_levels<true, NT>(Hh, n); else heapify_levels<false, NT>(Hh, n); }
-    if constexpr (kLds) {
-      if (tid < 64) { if (upward) heap_extract_pipelined<true>(Hh, n, k); else heap_extract_pipelined<false>(Hh, n, n - k); }
-    } else {
-      if (tid == 0) { if (upward) heap_extract_serial<true>(Hh, n, k); else heap_extract_serial<false>(Hh, n, n - k); }
-    }
-    __syncthreads();
-  };
-  if (n <= heap_cap) run(Hl); else run(Hg);
-}
+namespace {
 
-// the multipath kernel's per-frame view of the launch constants (see xargs_now() in beam_exact.hip)
-#define XBEAM_MP_VIEWS(KA)                                                                                           \
-  const LexDev &lx = (KA).lx; const XWork &xw = (KA).xw; const Work &wk = xw.w;                                        \
-  XSv<WIDE> sv;                                                                                                       \
-  if constexpr (WIDE) sv.p = reinterpret_cast<u32x4 *>(ub + wk.o_sv); else sv.p = (lds_v4 *)dyn_lds;                    \
-  lds_i32 *welist = (lds_i32 *)(dyn_lds + xw.off_we);      /* token ids of the frame's word ends; the final cut returns its order here */ \
-  lds_i32 *dbase = (lds_i32 *)(dyn_lds + xw.off_dbase);                                                                \
-  lds_u32 *tpre = (lds_u32 *)(dyn_lds + xw.off_tpre);                                                                  \
-  XCells cl;                                                                                                          \
-  cl.ub = ub; cl.o_nodekey = wk.o_nodekey; cl.o_nodefirst = xw.o_nodefirst; cl.o_touched = wk.o_touched;               \
-  cl.nslot = xw.nslot;                                                                                                \
-  cl.lkey = (lds_u64 *)(dyn_lds + xw.off_cells);                                                                       \
-  cl.lnode = (lds_i32 *)(dyn_lds + xw.off_lnode);                                                                      \
-  cl.lfirst = (lds_u32 *)(dyn_lds + xw.off_lfirst);                                                                    \
-  lds_f32 *rowc = (lds_f32 *)(dyn_lds + xw.off_row);                                                                   \
-  PruneMem pm;                                                                                                        \
-  pm.compR = (lds_u64 *)(dyn_lds + xw.off_compr); pm.compT = pm.compR + xw.b_cap;                                      \
-  pm.vposR = (lds_u32 *)(dyn_lds + xw.off_vpos);                                                                       \
-  pm.idR = (lds_u32 *)(dyn_lds + xw.off_id);                                                                           \
-  pm.idT = (lds_u32 *)(dyn_lds + xw.off_idt);                                                                          \
-  pm.hist = (lds_u32 *)(dyn_lds + xw.off_hist);                                                                        \
-  pm.tailmask = (lds_u32 *)(dyn_lds + xw.off_tail);                                                                    \
-  pm.cand = (lds_i32 *)(pm.tailmask + (xw.w.beam + 31) / 32 + 2);                                                      \
-  pm.occ = pm.cand + kMaxCand; pm.need = pm.occ + kMaxCand; pm.takers = pm.need + kMaxCand + 4;                        \
-  pm.ordv = pm.takers + (kMaxCand + 1) * (kTakers + 1);                                                                \
-  pm.b_cap = xw.b_cap;                                                                                                \
-  pm.sw_region = (unsigned char JAMD_LDS *)(dyn_lds + xw.off_dov); pm.sw_bytes = xw.off_row - xw.off_dov;             \
-  pm.sw_glob = xw.o_sweep ? ub + xw.o_sweep : nullptr;                                                                 \
-  pm.pstat = xw.o_sweep ? sh.pst : nullptr;                                                                           \
-  lds_u64 *Hlds = (lds_u64 *)(dyn_lds + xw.off_heap);                                                                  \
-  unsigned long long *Hglob = reinterpret_cast<unsigned long long *>(ub + xw.o_heap);                                  \
-  u32x4 *Gcol = reinterpret_cast<u32x4 *>(ub + xw.o_collect);                                                          \
-  auto clear_cells = [&]() { for (int i = tid; i < cl.nslot; i += NT) { cl.lkey[i] = 0ull; cl.lnode[i] = -1; cl.lfirst[i] = 0u; } }; \
-  const float lmw = lx.lm_weight, pen = lx.lm_penalty;                                                                 \
-  const int lmt = lx.lm_type & 0xff;                                                                                  \
-  const bool dfa = lmt != JAMD_LM_NGRAM;                                                                               \
-  const bool wordmode = lmt == JAMD_LM_WORD;                                                                           \
-  unsigned long long *memo = reinterpret_cast<unsigned long long *>(ub + wk.o_lmcache);                                \
-  const int s1 = xw.s1, XW = xw.xw;                                                                                    \
-  const unsigned submask = (1u << s1) - 1u;                                                                            \
-  const int nroot_x = wordmode ? 0 : (dfa ? lx.startnum : lx.isolatenum);                                              \
-  const int slots2 = nroot_x * XW;                         /* visiting indices a word end owns in the second half */ \
-  lds_u32 *bm_l = (lds_u32 *)(dyn_lds + xw.off_bm);                                                                    \
-  unsigned *bm_g = reinterpret_cast<unsigned *>(ub + xw.o_bitmap);                                                     \
-  (void)welist; (void)dbase; (void)tpre; (void)rowc; (void)Hlds; (void)Hglob; (void)Gcol; (void)lmw; (void)pen; (void)memo; \
-  (void)XW; (void)submask; (void)slots2; (void)bm_l; (void)bm_g; (void)clear_cells
-
-template <bool TIMED, bool WIDE, int NT>
-__global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(4, 4)))
-beam_exact_mp_kernel(XKArgs ka_, const float *__restrict__ scores, int S, const int *__restrict__ utt_off, int smode) {
-  __shared__ XShared sh;
-  extern __shared__ __align__(16) unsigned char dyn_lds[];
-#if JAMD_XARGS_RELOAD
-  const XKArgs &ka0 = xargs_now();
-#else
-  const XKArgs &ka0 = ka_;
-#endif
-  if (threadIdx.x == 0 && ka0.xw.w.resident) __hip_atomic_fetch_add(ka0.xw.w.resident, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-  const int u = min(max(utt_off[gridDim.x + 1 + blockIdx.x], 0), (int)gridDim.x - 1);
-  int tid = threadIdx.x;
-  const int t_begin = utt_off[u], nrows = utt_off[u + 1] - t_begin;
-  StreamState *ss = smode ? ka0.xw.w.stream + u : nullptr;
-  const bool resume = smode && ss->started;
-  const int base = resume ? ss->frames_done : 0;
-  const int T = base + nrows;
-  const bool finish = smode != 1;
-  unsigned char *const ub = ka0.xw.w.slices + (size_t)u * ka0.xw.w.utt_stride;
 #define NODETOK(i) SLICE(unsigned, xw.o_nodetok, i)       /* i = TGT(node) >= 0 */
 #define TGT(node) lx.at<int>(xw.o_mp_tgt, node)
 #define ARR(i) SLICE(int, xw.o_arr, i)
 #define KEY2(i) SLICE(unsigned, xw.o_key2, i)
-  jamd_pass1_result *res = ka0.xw.w.res + u;
-  XBEAM_MP_VIEWS(ka0);
-  int *const pstat_glob = xw.o_sweep ? reinterpret_cast<int *>(ub + xw.o_pstat) : nullptr;
-  if (tid == 0) for (int i = 0; i < 16; i++) sh.pst[i] = 0;
+
+// K6m's per-frame views: the common part, the visiting indices of the second half and the creation-order bitmap
+#define XBEAM_MP_VIEWS(KA)                                                                                            \
+  XBEAM_VIEWS_COMMON(KA, lx.lm_type & 0xff, , auto clear_cells = [&]() { for (int i = tid; i < cl.nslot; i += NT) { cl.lkey[i] = 0ull; cl.lnode[i] = -1; cl.lfirst[i] = 0u; } };); \
+  const int slots2 = nroot_x * XW;                         /* visiting indices a word end owns in the second half */  \
+  lds_u32 *bm_l = (lds_u32 *)(dyn_lds + xw.off_bm);                                                                   \
+  unsigned *bm_g = reinterpret_cast<unsigned *>(ub + xw.o_bitmap);                                                    \
+  (void)slots2; (void)bm_l; (void)bm_g; (void)clear_cells
+
+template <bool TIMED, bool WIDE, int NT>
+__global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(4, 4)))
+beam_exact_mp_kernel(XKArgs ka_, const float *__restrict__ scores, int S, const int *__restrict__ utt_off, int smode) {
+  XBEAM_ENTRY(XBEAM_MP_VIEWS);
   const int head_root = dfa ? -1 : lx.word_head(lx.head_silwid);
 
   if (resume) {
-    if (!ss->active) return;
-    if constexpr (!WIDE) {
-      const u32x4 *src = (const u32x4 *)(ub + wk.o_sv);
-      for (int i = tid; i < wk.sv_bytes / 16; i += NT) sv.p[i] = src[i];
-    }
-    if (tid == 0) { sh.n_atom = ss->n_atom; sh.n_surv = ss->n_surv; }
-    clear_cells();
-    __syncthreads();
+    XBEAM_RESUME(clear_cells());
   } else {
-    if (tid == 0) {
-      sh.n_atom = 0; sh.n_surv = 0;
-      res->status = JAMD_PASS1_OK; res->natom = 0; res->wnum = 0; res->score = JAMD_LOG_ZERO;
-      res->died_at = -1; res->ties = 0; res->ties_node = 0; res->ties_wordend = 0; res->ties_cut = 0;
-      res->frames = T; res->max_tokens = 0;
-      for (int i = 0; i < 8; i++) res->phase_us[i] = 0;
-    }
-    for (int i = tid; i < wk.nscword; i += NT) memo[i] = 0xffffffff00000000ull;
     // (an utterance can end between steps C1 and O -- the transition-only last call, an overflow -- and leave entries behind)
-    for (int i = tid; i < xw.n_mp_tgt; i += NT) NODETOK(i) = 0u;
-    __syncthreads();
-    if (nrows <= 0) {
-      if (tid == 0) { if (smode != 1) res->status = JAMD_PASS1_FAIL; if (ss) { ss->started = 0; ss->active = 1; } }
-      return;
-    }
+    XBEAM_RESET(for (int i = tid; i < xw.n_mp_tgt; i += NT) NODETOK(i) = 0u);
     // get_back_trellis_init(): the initial tokens carry the LM score only (init_nodescore :1657-1663, :1733-1737), then
     // sort_token_no_order() (:1807)
     if (!dfa) {
@@ -216,31 +118,15 @@ beam_exact_mp_kernel(XKArgs ka_, const float *__restrict__ scores, int S, const 
       __syncthreads();
     }
   }
-  float thr = resume ? ss->thr : JAMD_LOG_ZERO;
-  // the phase clocks of the instrumented instantiation live in LDS (thread 0 adds to them): eight 64-bit counters in
-  // registers cost the kernel 16 VGPRs it does not have
-  unsigned long long *const ph = sh.ph;
-  if (TIMED && threadIdx.x == 0) for (int i = 0; i < 8; i++) sh.ph[i] = 0ull;
-  unsigned long long tc = wall_clock64(), tc2 = tc;
-  (void)tc2;
-  int max_tokens = resume ? ss->max_tokens : 1;
-  bool stopped = false;
+  XBEAM_LOOP_STATE();
   __syncthreads();
 
-  auto row_request = [&](int tt) {
-    if (!wk.row_cache || tt >= T) return;
-    const float *rg = scores + (size_t)(t_begin + tt - base) * S;
-    const int ln = tid & 63;
-    for (int b = uni((int)(tid >> 6)) * 64; b < S; b += NT)
-      if (b + ln < S) __builtin_amdgcn_global_load_lds((glb_void *)(rg + b + ln), (lds_void *)(rowc + b), 4, 0, 0);
-  };
+  XBEAM_ROW_REQUEST();
   row_request(base);
 
   for (int t = base; t <= (finish ? T : T - 1); t++) {
     tid = tid_now();
-#if JAMD_XARGS_RELOAD
     XBEAM_MP_VIEWS(xargs_now());                           // this frame's view of the launch constants
-#endif
     const int n_surv = uni(sh.n_surv);
     __syncthreads();
     if (tid == 0) {
@@ -675,82 +561,11 @@ beam_exact_mp_kernel(XKArgs ka_, const float *__restrict__ scores, int S, const 
   }
   __syncthreads();
 
-  if (smode == 1) {
-    if constexpr (!WIDE) {
-      if (!stopped) {
-        u32x4 *dst = (u32x4 *)(ub + wk.o_sv);
-        for (int i = tid; i < wk.sv_bytes / 16; i += NT) dst[i] = sv.p[i];
-      }
-    }
-    if (tid == 0) {
-      ss->started = 1; ss->active = stopped ? 0 : 1; ss->frames_done = T; ss->n_surv = sh.n_surv; ss->thr = thr;
-      ss->n_atom = sh.n_atom; ss->ties = 0; ss->ties_we = 0; ss->ties_cut = 0;
-      ss->max_tokens = max_tokens;
-      res->natom = min(sh.n_atom, wk.atom_cap); res->frames = T; res->max_tokens = max_tokens;
-      res->ties = 0;
-      if (TIMED) for (int i = 0; i < 8; i++) res->phase_us[i] += (int)(ph[i] / 100ull);
-      if (pstat_glob) for (int i = 0; i < 16; i++) pstat_glob[i] += sh.pst[i];
-    }
-    return;
-  }
-  if (ss && tid == 0) { ss->active = 0; ss->started = 1; ss->frames_done = T; }
-
-  // ---- find_1pass_result() :399-455 + trace_backptr() :294-340
-  const int natom = min(sh.n_atom, wk.atom_cap);
-  if (tid == 0) sh.best_atom = -1;
-  __syncthreads();
-  if (res->status == JAMD_PASS1_OK && dfa) {
-    if (tid == 0) { sh.n_arc = -1; sh.we_best = 0ull; }
-    __syncthreads();
-    int lt = -1;
-    for (int i = tid; i < natom; i += NT)
-      if (ATOM(i).backscore > JAMD_LOG_ZERO && ATOM(i).endtime > lt) lt = ATOM(i).endtime;
-    if (lt >= 0) atomicMax(&sh.n_arc, lt);
-    __syncthreads();
-    lt = sh.n_arc;
-    for (int i = tid; i < natom; i += NT)
-      if (ATOM(i).endtime == lt && ATOM(i).backscore > JAMD_LOG_ZERO)
-        atomicMax(&sh.we_best, ((unsigned long long)ord(ATOM(i).backscore) << 32) | (0xffffffffu - (unsigned)ATOM(i).wid));
-    __syncthreads();
-    const unsigned long long kb = sh.we_best;
-    for (int i = tid; i < natom; i += NT)
-      if (kb != 0ull && ATOM(i).endtime == lt && (unsigned)ATOM(i).wid == 0xffffffffu - (unsigned)kb &&
-          ord(ATOM(i).backscore) == (unsigned)(kb >> 32)) sh.best_atom = i;
-  } else if (res->status == JAMD_PASS1_OK) {
-    int bt = -1;
-    for (int i = tid; i < natom; i += NT)
-      if (ATOM(i).wid == lx.tail_silwid && ATOM(i).backscore > JAMD_LOG_ZERO && ATOM(i).endtime > bt) bt = ATOM(i).endtime;
-    if (tid == 0) sh.n_arc = -1;
-    __syncthreads();
-    if (bt >= 0) atomicMax(&sh.n_arc, bt);
-    __syncthreads();
-    bt = sh.n_arc;
-    for (int i = tid; i < natom; i += NT)
-      if (bt >= 0 && ATOM(i).wid == lx.tail_silwid && ATOM(i).backscore > JAMD_LOG_ZERO && ATOM(i).endtime == bt) sh.best_atom = i;
-  }
-  __syncthreads();
-  if (tid == 0) {
-    res->natom = natom; res->ties = 0; res->max_tokens = max_tokens;
-    res->ties_node = 0; res->ties_wordend = 0; res->ties_cut = 0;
-    if (pstat_glob) for (int i = 0; i < 16; i++) pstat_glob[i] += sh.pst[i];
-    if (TIMED) for (int i = 0; i < 8; i++) res->phase_us[i] += (int)(ph[i] / 100ull);
-    res->frames = T;
-    if (sh.n_atom > wk.atom_cap) res->status = JAMD_PASS1_OVERFLOW;
-    if (res->status == JAMD_PASS1_OK) {
-      const int best = sh.best_atom;
-      if (best < 0) res->status = JAMD_PASS1_FAIL;
-      else {
-        int n = 0, a = best;
-        int rev[MAXSEQ];
-        rev[n++] = ATOM(a).wid;
-        while (ATOM(a).begintime > 0 && n < MAXSEQ) { a = ATOM(a).last_tre; rev[n++] = ATOM(a).wid; }
-        for (int k = 0; k < n; k++) res->wseq[k] = rev[n - 1 - k];
-        res->wnum = n; res->score = ATOM(best).backscore;
-      }
-    }
-  }
+  XBEAM_END(, );
 #undef NODETOK
 #undef TGT
 #undef ARR
 #undef KEY2
 }
+
+}  // namespace

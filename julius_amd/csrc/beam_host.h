@@ -1,7 +1,7 @@
 // beam_host.h -- the host side of the first pass: the lexicon (beam_lexicon.hip), the work area and the C ABI over it
 // (beam_api.hip), and the interfaces through which beam_api.hip reaches the kernels: beam.hip (the canonical-tie kernel
-// K6, fbeam_*), beam_strict.hip (the strict-order cross-check, sbeam_*) and beam_exact.hip (the exact-order kernels,
-// xbeam_* in beam_exact.h).  Internal, not installed.
+// K6, fbeam_*), beam_strict.hip (the strict-order cross-check, sbeam_*) and beam_exact.hip / beam_exact_layout.hip (the exact-order
+// kernels and their LDS layout, xbeam_* in beam_exact.h).  Internal, not installed.
 #pragma once
 #include <vector>
 

@@ -1,10 +1,11 @@
 // beam_sweep.h -- the events of the extraction loop of sort_token_upward() (libjulius/src/beam.c:1368-1383), ALL AT ONCE.
-// Included by beam_exact.hip behind its helpers (block scans, prekey(), tid_now()).
+// Brought in by beam_prune.h, inside its anonymous namespace and behind the helpers this file uses (XShared, the block
+// scans and tid_now() of beam_exact_dev.h; prekey(), the heap routines): not meant to be included on its own.
 //
-// beam_exact.hip replaces the extraction loop by its closed form: the top elements come out sorted by (score, pre-order
+// exact_prune() (beam_prune.h) replaces the extraction loop by its closed form: the top elements come out sorted by (score, pre-order
 // of their heap position), except for "events" -- a turn i whose tail position n - i + 1 still holds a top element x:
 // x is taken off its leaf and re-inserted from the root (it sinks past strictly greater elements along the path of
-// larger children and stops at `h`).  The wave-serial replay in beam_exact.hip handles a few dozen tail candidates; a
+// larger children and stops at `h`).  The wave-serial replay in beam_prune.h handles a few dozen tail candidates; a
 // wide beam over a 20k-word lexicon has hundreds per frame (a tenth of the top 4000 sit on tail leaves), and replaying
 // them one after the other costs more than the loop itself.  This file resolves them together.
 //

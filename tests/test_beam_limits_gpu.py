@@ -164,7 +164,7 @@ def limits(big):
     lim["narrow"] = _last_true(lambda b: _layout(big, b) == "narrow", 1, 65536)
     lim["max"] = _last_true(lambda b: _layout(big, b) != "none", lim["narrow"], 65536)
     lim["half"] = _last_true(lambda b: _half_ok(big, b), 1, lim["max"] + 1)
-    # the closed-form extraction needs room for the top lists (b_cap > 0, beam_exact.hip xbeam_place_with()): past it every
+    # the closed-form extraction needs room for the top lists (b_cap > 0, beam_exact_layout.hip xbeam_place_with()): past it every
     # pruned frame goes to the extraction loop
     lim["closed"] = _last_true(lambda b: _closed_form_frames(big, b) > 0, lim["narrow"] + 1, lim["max"])
     print(f"\nexact-order limits on the {big.lex['nword']}-word lexicon ({big.lex['nnode']} nodes): "

@@ -1,5 +1,5 @@
 """The closed form of sort_token_upward()'s extraction loop that the exact-order first-pass kernel uses
-(julius_amd/csrc/beam_exact.hip, DESIGN.md section 3 "K6x"), restated in plain Python and checked against the
+(julius_amd/csrc/beam_prune.h, DESIGN.md section 3 "K6x"), restated in plain Python and checked against the
 oracle's sequential restatement of libjulius/src/beam.c:1342-1516 on tie-heavy random inputs.  CPU only.
 
 Model.  After heapify, let B = the elements with score >= the k-th largest, each with its heap position ("virtual
@@ -129,7 +129,7 @@ def test_closed_form_equals_sequential_heap(oracle, seed):
 
 
 def heapify_overlapped(score, split=3):
-    """The schedule of heapify_overlapped() in beam_exact.hip, lane by lane: the sift-downs of ALL levels of a subtree
+    """The schedule of heapify_overlapped() in beam_prune.h, lane by lane: the sift-downs of ALL levels of a subtree
     run together, the sift of depth L starting one step after the sifts of depth L + 1; within a step every active
     sift first READS the two children of its hole (all reads see the state left by the previous step), then all
     WRITE.  Subtrees rooted at depth `split` first (independent of each other), then depths split-1 .. 0."""
@@ -190,7 +190,7 @@ def test_overlapped_heapify_equals_sequential(seed):
 
 @pytest.mark.parametrize("seed", range(6))
 def test_whole_array_model_equals_sequential_heap(seed):
-    """The model behind exact_prune<FULL> (csrc/beam_exact.hip, beam_sweep.h; the multipath frame's mid-frame sort needs
+    """The model behind exact_prune<FULL> (csrc/beam_prune.h, beam_sweep.h; the multipath frame's mid-frame sort needs
     tindex[] WHOLE): the extracted part = the sweep replay's extraction order, the residual heap = every non-event turn's
     tail element sifted down from where the hole left the extracted region -- in pure Python (tools/prune_lab2.py) against
     the sequential loop of sort_token_upward() / _downward() (beam.c:1342-1480), both directions, from distinct scores to

@@ -1,4 +1,4 @@
-"""The rank-pruning step of the exact-order first-pass kernel (beam_exact.hip: level-parallel heapify +
+"""The rank-pruning step of the exact-order first-pass kernel (beam_prune.h: level-parallel heapify +
 closed-form extraction with replayed tail events) against the oracle's sequential restatement of
 sort_token_no_order() (libjulius/src/beam.c:1342-1516), on score vectors full of exact ties."""
 import numpy as np

@@ -1,6 +1,8 @@
 #!/bin/bash
 # development: build/variants/<name>.so = the product library with ONE source file (default beam_exact.hip) compiled with
 # -DJAMD_DEV and extra flags.   usage: [SRC=julius_amd/csrc/dnn.hip] tools/build_variant.sh name -DJAMD_XBEAM_PROBE=1 ...
+# beam_exact.hip is the unit of both exact-order kernels (K6x; K6m from beam_exact_mp.h) and of the pruning step (beam_prune.h,
+# beam_sweep.h): the knobs JAMD_XBEAM_PROBE, JAMD_XPROBES and JAMD_XBEAM_CB all act through it.
 set -eu
 name=$1; shift
 cd "$(dirname "$0")/.."

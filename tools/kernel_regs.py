@@ -6,7 +6,12 @@
 Unbundles the gfx950 code object (clang-offload-bundler for .o files, the .hip_fatbin section for the shared library)
 and prints, per kernel: VGPRs, AGPRs, SGPRs, SGPR spills, VGPR spills, scratch bytes per thread, static LDS bytes, instruction
 count (llvm-objdump).  --diff OTHER compares against a second library kernel by kernel: those figures and the
-instruction text (addresses and encodings stripped); it lists what differs and exits 1 if anything does."""
+instruction text (addresses and encodings stripped); it lists what differs and exits 1 if anything does.
+
+The exact-order first-pass kernels (--filter beam_exact, --filter prune_order) are all compiled by csrc/beam_exact.hip, from
+beam_exact_dev.h, beam_prune.h, beam_sweep.h and beam_exact_mp.h.  A call of a function that is not inlined is encoded
+relative to the call site, so moving a kernel to another unit -- or changing the order of the kernels in one -- changes its
+text here even when nothing else does."""
 import argparse
 import hashlib
 import json
