@@ -212,6 +212,9 @@ int jamd_gms_create(jamd_engine *e, const jamd_gmm_desc *gs, const int *state2gs
   if (gs->nbook > 0 || gs->nstream != 1) { jamd_set_error("jamd_gms_create: the selection model must be a plain single-stream GMM"); return JAMD_EINVAL; }
   for (int s = 0; s < nstate; s++)
     if (state2gs[s] >= gs->nstate) { jamd_set_error("jamd_gms_create: state2gs[%d] out of range", s); return JAMD_EINVAL; }
+  // compute_g_max() starts from a state's last entry: the reference's reader cannot produce a state without one
+  for (int i = 0; gs->st_off && i < gs->nstate; i++)
+    if (gs->st_off[i + 1] - gs->st_off[i] < 1) { jamd_set_error("jamd_gms_create: selection state %d has no Gaussians", i); return JAMD_EINVAL; }
   JAMD_HIP(hipSetDevice(e->device));
   jamd_gms *m = new jamd_gms();
   m->eng = e; m->Sgs = gs->nstate; m->Egs = gs->nentry; m->S = nstate; m->nbest = nbest;

@@ -97,6 +97,10 @@ def test_bad_arguments(engine, fixture):
     bad[0] = 10000
     with pytest.raises(lib.JamdError):
         lib.Gms(engine, fixture["gs"], bad, 8)
+    empty = dict(fixture["gs"], st_off=fixture["gs"]["st_off"].copy())
+    empty["st_off"][2] = empty["st_off"][1]                     # a hand-written descriptor: state 1 without an entry
+    with pytest.raises(lib.JamdError, match=r"\(-1\).*jamd_gms_create: selection state 1 has no Gaussians"):
+        lib.Gms(engine, empty, z["state2gs"], 8)
     stage = lib.Gms(engine, fixture["gs"], z["state2gs"], 8)
     with pytest.raises(lib.JamdError):
         stage.apply_host(z["frames"][:10], np.zeros((10, stage.S), np.float32), utt_off=[0, 5])

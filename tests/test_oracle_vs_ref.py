@@ -4,6 +4,7 @@ the dev container builds from /root/reference (oracle/Makefile)."""
 import numpy as np
 import pytest
 
+from densref import dens_ref, gmax_winners, visiting_order_covered
 from julius_amd import synth
 from oracle import pyoracle as po
 
@@ -113,16 +114,16 @@ def test_gmm_blob_roundtrip(ref, tmp_path):
             assert np.array_equal(a["st_book"], b["st_book"])
 
 
-@pytest.mark.parametrize("nbest", [4, 8, 24])
-def test_gaussian_mixture_selection(oracle, ref, tmp_path, nbest):
-    """-gshmm / -gsnum: gms_state() (gms.c:394) returns the real score for states whose selection
-    state is among the nbest of the frame and the selection state's score otherwise."""
+def _gms_case(oracle, ref, tmp_path, nbest, **gs_args):
+    """One selection model against the compiled reference on three utterances; returns what the caller needs to
+    judge the inputs: the exported selection data, the utterances and their frame offsets."""
     task = synth.make_triphone_task(tmp_path, seed=5, nword=60)
-    gpath, _ = synth.make_gs_model(task, seed=5)
+    gpath, _ = synth.make_gs_model(task, seed=5, **gs_args)
     am = ref.am_load(task["hmmdefs"], task["hmmlist"], gshmm=gpath, gms_num=nbest)
     gs = am.gms()
     assert gs["nbest"] == nbest and len(gs["model"]["st_off"]) - 1 == 78
     full_model = ref.am_load(task["hmmdefs"], task["hmmlist"]).export()
+    frames = []
     for u in range(3):
         fr, _ = synth.make_utterance(task, nwords=2 + u, seed=50 + u)
         want = am.outprob(fr)
@@ -130,6 +131,34 @@ def test_gaussian_mixture_selection(oracle, ref, tmp_path, nbest):
         used = gs["state2gs"] >= 0              # states outside every model: the reference reads out of bounds
         assert np.array_equal(got[:, used], want[:, used])
         assert 0.0 < (got[:, used] != oracle.gmm_outprob(full_model, fr)[:, used]).mean() < 1.0
+        frames.append(fr)
+    return gs, np.concatenate(frames), np.cumsum([0] + [len(f) for f in frames])
+
+
+@pytest.mark.parametrize("nbest", [4, 8, 24])
+def test_gaussian_mixture_selection(oracle, ref, tmp_path, nbest):
+    """-gshmm / -gsnum: gms_state() (gms.c:394) returns the real score for states whose selection
+    state is among the nbest of the frame and the selection state's score otherwise."""
+    _gms_case(oracle, ref, tmp_path, nbest)
+
+
+@pytest.mark.parametrize("nbest", [4, 24])
+@pytest.mark.parametrize("M,ragged,null_frac", [(16, False, 0.0), (9, True, 0.0), (9, True, 0.15)])
+def test_gaussian_mixture_selection_many_mixtures(oracle, ref, tmp_path, nbest, M, ragged, null_frac):
+    """The same at the mixture counts of a real selection model, where compute_g_max()'s visiting order
+    (gms_gprune.c:151-174: last frame's winner, then mix_num-1 .. 0 under a strict >) spans several groups of the
+    device's four-wide loop -- the three-Gaussian model above never enters it.  The last case holds NULL densities:
+    the reference reads them back from missing <Mixture> entries and calc_contprob_with_safe_pruning() scores them
+    LOG_ZERO before it looks at anything else (gms_gprune.c:104), so they are deterministic and compared here too.
+    The inputs must exercise the order: the winners of one state fall in all four classes of (n - 1 - k) % 4, inside
+    four-wide groups and in the scalar tail, and a winner changes from one frame to the next."""
+    gs, fr, utt_off = _gms_case(oracle, ref, tmp_path, nbest, M=M, ragged=ragged, null_frac=null_frac)
+    m = gs["model"]
+    assert int(np.diff(m["st_off"]).max()) == M and ((m["ent_dens"] < 0).any() == (null_frac > 0))
+    win, _ = gmax_winners(m["st_off"], dens_ref(m, fr), utt_off)
+    residues, changed, in_body, in_tail = visiting_order_covered(m["st_off"], win, utt_off)
+    assert residues == {0, 1, 2, 3} and changed and in_body
+    assert in_tail or M % 4 == 0 and not ragged
 
 
 @pytest.mark.parametrize("num,null_frac", [(1, 0.0), (3, 0.2), (10, 0.0), (64, 0.1)])

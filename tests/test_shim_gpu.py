@@ -588,18 +588,11 @@ def test_official_plugin_slot(tmp_path, kind):
 
 def test_per_gaussian_scores(engine):
     """jamd_gmm_dens_*: the values the plugin slot hands to calc_mix(), against an fp32 restatement
-    of compute_g_base() (gprune_none.c:59-82) in numpy, bit for bit."""
+    of compute_g_base() (gprune_none.c:59-82) in numpy (densref.py), bit for bit."""
+    from densref import dens_ref
     from julius_amd import lib
     model = synth.make_gmm(S=40, M=5, D=39, seed=7, ragged=True, null_frac=0.1)
     fr = synth.make_frames(model, T=70, seed=2)
     got = lib.Gmm(engine, model).dens_host(fr)
-    dens = model["ent_dens"]
-    acc = np.where(dens >= 0, model["gconst"][np.maximum(dens, 0)], np.float32(0))[None, :].repeat(len(fr), 0).astype(np.float32)
-    for d in range(fr.shape[1]):
-        x = (fr[:, None, d] - model["mean"][np.maximum(dens, 0), d][None, :]).astype(np.float32)
-        x = (x * x).astype(np.float32)
-        x = (x * model["ivar"][np.maximum(dens, 0), d][None, :]).astype(np.float32)
-        acc = (acc + x).astype(np.float32)
-    want = (acc * np.float32(-0.5)).astype(np.float32)
-    want[:, dens < 0] = np.float32(-1000000.0)
+    want = dens_ref(model, fr)
     assert np.array_equal(got, want)
