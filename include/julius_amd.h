@@ -145,7 +145,12 @@ int  jamd_gmm_veclen(const jamd_gmm *g);
  * outprob_cache[t][s] via calc_mix() (calc_mix.c:41) / calc_tied_mix()
  * (calc_tied_mix.c:162) with the batch loop outprob.c:230-242.
  * frames is [T][veclen] row-major, out is [T][nstate] row-major (the
- * outprob_cache layout, outprob.c:127-129). */
+ * outprob_cache layout, outprob.c:127-129).
+ * The model's device scratch (the per-Gaussian scores of a call of at most 256 frames, the codebook cache of a
+ * tied-mixture model, the staged utterance boundaries) is reused by every call: calls on one jamd_gmm must not be in
+ * flight on two streams at once -- queue them on one stream (they are then ordered), or use one object per stream.
+ * The first call of at most 256 frames allocates its scratch (256 x the model's mixture entries, floats); a growing
+ * codebook cache allocates as well: such a call is not free of device allocation. */
 int  jamd_gmm_outprob_dev(jamd_gmm *g, const float *dev_frames, int T, float *dev_out,
                           void *stream);
 /* The same for a BATCH of utterances laid back to back: utterance u owns frames utt_off[u]..utt_off[u+1]) (utt_off is

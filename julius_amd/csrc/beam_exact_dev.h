@@ -126,13 +126,6 @@ __device__ __forceinline__ T JAMD_LDS *uni(T JAMD_LDS *p) {
   return (T JAMD_LDS *)(unsigned long)(unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(unsigned long)p);
 }
 
-// the LDS operations of one wave execute in order: this only keeps the compiler from moving them across
-__device__ __forceinline__ void wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 __device__ __forceinline__ unsigned ordz(float f) { return ord(f + 0.0f); }   // -0.0 and +0.0 compare equal as floats
 
 // Candidates for one node: key = the best of them (score bits || ~visiting index), nfirst = ~(their earliest

@@ -339,15 +339,6 @@ dnn_norm_kernel(float *__restrict__ x, const float *__restrict__ lse, const floa
   }
 }
 
-int ensure(float **p, size_t *cap, size_t need) {
-  if (*cap >= need) return JAMD_OK;
-  if (*p) JAMD_HIP(hipFree(*p));
-  *p = nullptr; *cap = 0;
-  JAMD_HIP(hipMalloc(p, need));
-  *cap = need;
-  return JAMD_OK;
-}
-
 }  // namespace
 
 extern "C" {
@@ -432,7 +423,7 @@ int jamd_dnn_outprob_dev(jamd_dnn *n, const float *dev_frames, int T, float *dev
   // hidden activations ping-pong between two [T][maxhidden] buffers
   int maxh = 1;
   for (int l = 1; l < n->nlayer; l++) if (8 * n->kmp[l] > maxh) maxh = 8 * n->kmp[l];
-  if ((rc = ensure(&n->d_xr, &n->xr_cap, sizeof(float) * (size_t)T * 8 * n->kmp[0])) != JAMD_OK) return rc;
+  if ((rc = jamd_grow(&n->d_xr, &n->xr_cap, sizeof(float) * (size_t)T * 8 * n->kmp[0])) != JAMD_OK) return rc;
   const size_t need = sizeof(float) * (size_t)T * maxh;
   if (n->act_cap < need) {
     for (int k = 0; k < 2; k++) { if (n->d_act[k]) JAMD_HIP(hipFree(n->d_act[k])); n->d_act[k] = nullptr; }
@@ -441,7 +432,7 @@ int jamd_dnn_outprob_dev(jamd_dnn *n, const float *dev_frames, int T, float *dev
     JAMD_HIP(hipMalloc(&n->d_act[1], need));
     n->act_cap = need;
   }
-  if ((rc = ensure(&n->d_lse, &n->lse_cap, sizeof(float) * (size_t)T)) != JAMD_OK) return rc;
+  if ((rc = jamd_grow(&n->d_lse, &n->lse_cap, sizeof(float) * (size_t)T)) != JAMD_OK) return rc;
   // The output layer is followed by the serial row log-sum (dnn_lse: one lane per frame, a
   // latency-bound chain of table gathers that keeps ~1 wave per CU busy) and the
   // normalisation.  For very long batches (>= 131072 frames) the frames are cut into up to 8 chunks of 32768+ frames; chunk c's tail
@@ -523,8 +514,8 @@ int jamd_dnn_outprob_host(jamd_dnn *n, const float *host_frames, int T, float *h
   JAMD_HIP(hipSetDevice(n->eng->device));
   const int D = n->dims[0], S = n->dims[n->nlayer];
   int rc;
-  if ((rc = ensure(&n->d_frames, &n->frames_cap, sizeof(float) * (size_t)T * D)) != JAMD_OK) return rc;
-  if ((rc = ensure(&n->d_out, &n->out_cap, sizeof(float) * (size_t)T * S)) != JAMD_OK) return rc;
+  if ((rc = jamd_grow(&n->d_frames, &n->frames_cap, sizeof(float) * (size_t)T * D)) != JAMD_OK) return rc;
+  if ((rc = jamd_grow(&n->d_out, &n->out_cap, sizeof(float) * (size_t)T * S)) != JAMD_OK) return rc;
   hipStream_t st = n->eng->stream;
   JAMD_HIP(hipMemcpyAsync(n->d_frames, host_frames, sizeof(float) * (size_t)T * D, hipMemcpyHostToDevice, st));
   if ((rc = jamd_dnn_outprob_dev(n, n->d_frames, T, n->d_out, st)) != JAMD_OK) return rc;

@@ -1,0 +1,149 @@
+// gmm_dev.h -- device helpers of the Gaussian kernels (gmm_outprob.hip, gmm_pruned.hip, rejgmm.hip), each next to
+// the host-side twin that picks its template argument or its grid.  What the other scoring kernels and the first pass
+// share as well (addlog_step, finish_state, cd_reduce, wave_sync) is in jamd_device.h.  Internal, not installed.
+#pragma once
+#include <type_traits>
+
+#include "jamd_device.h"
+
+typedef float f2 __attribute__((ext_vector_type(2)));
+
+namespace jamd {
+
+// XCD-aware block decode: the dispatcher places block b on XCD b % 8
+// (MI355X_MICROARCH.md "Workgroup dispatch"); all frame-blocks of one state
+// range are given the same b % 8 so the range's records stay in that XCD's L2.
+__device__ __forceinline__ bool decode_block(int nfb, int nstb, int &fb, int &sb) {
+  const int b = blockIdx.x;
+  const int xcd = b & 7, q = b >> 3;
+  sb = xcd + 8 * (q / nfb);
+  fb = q % nfb;
+  return sb < nstb;
+}
+// ... and the grid it decodes: nfb frame-blocks for each of nstb ranges, the ranges rounded up to whole rounds of 8 XCDs
+static inline int xcd_grid(int nstb, int nfb) { return 8 * ((nstb + 7) / 8) * nfb; }
+
+// The vector lengths the kernels are compiled for: f(std::integral_constant<int, DT>) with DT = D for those, DT = 0
+// (run-time dimension, frames in LDS) for every other.
+template <typename F>
+static inline int dispatch_veclen(int D, F &&f) {
+  switch (D) {
+    case 39: return f(std::integral_constant<int, 39>{});
+    case 38: return f(std::integral_constant<int, 38>{});
+    case 26: return f(std::integral_constant<int, 26>{});
+    case 25: return f(std::integral_constant<int, 25>{});
+    default: return f(std::integral_constant<int, 0>{});
+  }
+}
+
+// Load the wave's 128 frames t0 .. t0 + 127 (clamped to T - 1): registers (DT>0) or LDS transposed
+// [d][128 frames of the wave] (DT==0, conflict-free ds_read_b32).
+template <int DT>
+__device__ __forceinline__ void load_frames(f2 *v, float *vt, const float *frames,
+                                            int t0, int T, int D, int lane) {
+  int ta = t0 + lane, tb = ta + 64;
+  if (ta > T - 1) ta = T - 1;
+  if (tb > T - 1) tb = T - 1;
+  const float *fa = frames + (size_t)ta * D, *fb = frames + (size_t)tb * D;
+  if constexpr (DT > 0) {
+#pragma unroll
+    for (int d = 0; d < DT; d++) { v[d].x = fa[d]; v[d].y = fb[d]; }
+  } else {
+    for (int d = 0; d < D; d++) { vt[d * 128 + lane] = fa[d]; vt[d * 128 + 64 + lane] = fb[d]; }
+    wave_sync();
+  }
+}
+
+// compute_g_base() (gprune_none.c:59-82) for a packed pair of frames held in
+// registers (DT > 0, compile-time dimension) or in LDS, transposed
+// [d][128 frames of the wave] (DT == 0, run-time dimension D).
+// r -> record [mean(D) ivar(D) gconst ...]; returns the two tmp*-0.5 scores,
+// LOG_ZERO for a NULL density (gconst stored as NaN).
+template <int DT>
+__device__ __forceinline__ f2 gauss_pair(const f2 *v, const float *vt, int lane, int D,
+                                         const float *__restrict__ r) {
+  const float gc = r[2 * D];
+  f2 acc = {gc, gc};
+  if constexpr (DT > 0) {
+#pragma unroll
+    for (int d = 0; d < DT; d++) {
+      const float mu = r[d], iv = r[DT + d];
+      f2 x = v[d] - f2{mu, mu};
+      x = x * x;
+      x = x * f2{iv, iv};
+      acc = acc + x;
+    }
+  } else {
+    for (int d = 0; d < D; d++) {
+      const float mu = r[d], iv = r[D + d];
+      f2 x = f2{vt[d * 128 + lane], vt[d * 128 + 64 + lane]} - f2{mu, mu};
+      x = x * x;
+      x = x * f2{iv, iv};
+      acc = acc + x;
+    }
+  }
+  f2 sc = {acc.x * -0.5f, acc.y * -0.5f};
+  if (gc != gc) sc = f2{JAMD_LOG_ZERO, JAMD_LOG_ZERO};
+  return sc;
+}
+
+// The output-tile epilogue: results of up to NS columns (states, mixture entries) x ROWS frames of one wave are staged
+// in a wave-private LDS tile [ROWS][NS + 1] and written as 64-byte row segments (a lane storing its own [t][s]
+// element makes 64 scattered 4-byte stores per instruction).  Rows t0 .. of out[][stride], columns c0 .. c0 + nc - 1.
+template <int NS, int ROWS>
+__device__ __forceinline__ void store_tile(const float (*tile)[NS + 1], float *out, int t0, int T,
+                                           int stride, int c0, int nc, int lane) {
+  wave_sync();                     // the tile's writes, visible to the other lanes
+  constexpr int RPI = 64 / NS;     // rows per store instruction
+  const int col = lane % NS, rsub = lane / NS;
+#pragma unroll 4
+  for (int it = 0; it < ROWS / RPI; it++) {
+    const int rr = it * RPI + rsub;
+    const int t = t0 + rr;
+    if (t < T && col < nc) out[(size_t)t * stride + c0 + col] = tile[rr][col];
+  }
+  wave_release();                  // read out before the next group of columns overwrites it
+}
+
+// cache_push() (gprune_common.c:88-126): keep the best `cap` (score,id) pairs
+// in descending order in a register-resident list of NMAX slots.
+//   bottom case (sc[len-1] >= score): append if there is room, else drop;
+//   otherwise insert before the first element that is not greater.
+template <int NMAX>
+__device__ __forceinline__ void topn_push(float (&sc)[NMAX], int (&id)[NMAX], int &len, int cap,
+                                          float score, int gid) {
+  int p;
+  float last = score;             // value of sc[len-1] (register array: no dynamic indexing)
+#pragma unroll
+  for (int i = 0; i < NMAX; i++) if (i == len - 1) last = sc[i];
+  if (len > 0 && last >= score) {
+    p = len;                      // bottom
+  } else {
+    p = 0;
+#pragma unroll
+    for (int i = 0; i < NMAX; i++) p += (i < len && sc[i] > score) ? 1 : 0;
+  }
+  if (p >= cap) return;
+#pragma unroll
+  for (int i = NMAX - 1; i >= 1; i--) {
+    if (i > p && i < cap) { sc[i] = sc[i - 1]; id[i] = id[i - 1]; }
+  }
+#pragma unroll
+  for (int i = 0; i < NMAX; i++) {
+    if (i == p) { sc[i] = score; id[i] = gid; }
+  }
+  if (len < cap) len++;
+}
+
+// ... and the NMAX a list of `cap` entries is instantiated with: cap rounded up to LO, .., 16, 32, 64 (LO = 2 or 4).
+template <int LO, typename F>
+static inline int dispatch_topn(int cap, F &&f) {
+  if constexpr (LO <= 2) if (cap <= 2) return f(std::integral_constant<int, 2>{});
+  if (cap <= 4) return f(std::integral_constant<int, 4>{});
+  if (cap <= 8) return f(std::integral_constant<int, 8>{});
+  if (cap <= 16) return f(std::integral_constant<int, 16>{});
+  if (cap <= 32) return f(std::integral_constant<int, 32>{});
+  return f(std::integral_constant<int, 64>{});
+}
+
+}  // namespace jamd

@@ -17,31 +17,13 @@
 //
 // Same lane = frame-pair mapping as the tile kernel: Gaussian records come
 // through scalar loads, the D-loop is packed VALU.
-#include "jamd_device.h"
+#include "gmm_dev.h"
+#include "gmm_host.h"
 
 namespace {
 using namespace jamd;
 
 constexpr int kWaves = 4;
-
-// Load the wave's 128 frames: registers (DT>0) or LDS transposed (DT==0).
-template <int DT>
-__device__ __forceinline__ void load_frames(f2 *v, float *vt, const float *__restrict__ frames,
-                                            int t0, int T, int D, int lane) {
-  int ta = t0 + lane, tb = ta + 64;
-  if (ta > T - 1) ta = T - 1;
-  if (tb > T - 1) tb = T - 1;
-  const float *fa = frames + (size_t)ta * D, *fb = frames + (size_t)tb * D;
-  if constexpr (DT > 0) {
-#pragma unroll
-    for (int d = 0; d < DT; d++) { v[d].x = fa[d]; v[d].y = fb[d]; }
-  } else {
-    for (int d = 0; d < D; d++) { vt[d * 128 + lane] = fa[d]; vt[d * 128 + 64 + lane] = fb[d]; }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-  }
-}
 
 // ---- plain states, gprune safe (top-`cap` by raw Gaussian score) ------------
 template <int DT, int NMAX>
@@ -51,9 +33,7 @@ gmm_safe_kernel(const float *__restrict__ rec, const int *__restrict__ st_off,
                 float *__restrict__ out, int T, int S, int D, int REC, int cap, int nsb,
                 float addmin_f) {
   extern __shared__ __align__(16) float dyn[];
-  // results of NS states x the wave's 128 frames are staged in a wave-private LDS tile and written as 64-byte
-  // row segments (a lane storing its own [t][s] element makes 64 scattered 4-byte stores per instruction)
-  constexpr int NS = 16;
+  constexpr int NS = 16;                    // states per output tile
   __shared__ float tile[kWaves][128][NS + 1];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int t0 = (blockIdx.x * kWaves + wave) * 128;
@@ -87,9 +67,9 @@ gmm_safe_kernel(const float *__restrict__ rec, const int *__restrict__ st_off,
     tile[wave][lane][si] = finish_state(y0);
     tile[wave][64 + lane][si] = finish_state(y1);
    }
-   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-   __builtin_amdgcn_wave_barrier();
-   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+   // (store_tile() in this kernel's own lines: inlined from the helper the loop's exit compare comes out inverted, and
+   // the kernel's instruction text is pinned to profiles/gmm_split_kernel_diff.txt)
+   wave_sync();
    constexpr int RPI = 64 / NS;              // rows per store instruction
    const int col = lane % NS, rsub = lane / NS;
 #pragma unroll 4
@@ -98,8 +78,7 @@ gmm_safe_kernel(const float *__restrict__ rec, const int *__restrict__ st_off,
      const int t = t0 + rr;
      if (t < T && col < ns) out[(size_t)t * S + sg + col] = tile[wave][rr][col];
    }
-   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-   __builtin_amdgcn_wave_barrier();
+   wave_release();
   }
 }
 
@@ -204,11 +183,7 @@ tmix_book_hist_kernel(const float *__restrict__ brec, const int *__restrict__ bo
   for (int i = lane; i < K; i += 64) calced[i] = 0;
   TopList L; L.sc = JAMD_LOG_ZERO; L.id = 0; L.len = 0; L.cap = cap;
   int last_id = 0, lnum = 0;              // lane j: winner j of the previous frame
-  auto sync = [] {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-  };
+  auto sync = [] { wave_sync(); };        // (a local name: called directly, two registers trade places in the kernel's pinned text)
   for (int t = t_begin; t < t_end; t++) {
     for (int d = lane; d < D; d += 64) x[d] = frames[(size_t)t * D + d];
     sync();
@@ -346,21 +321,16 @@ int launch_safe(jamd_gmm *g, const float *frames, int T, float *out, hipStream_t
   const dim3 grid(nfb, (g->S + nsb - 1) / nsb);
   const size_t dyn = DT > 0 ? 0 : sizeof(float) * kWaves * g->D * 128;
   const int cap = g->gprune_num < g->maxmix ? g->gprune_num : g->maxmix;
-#define JAMD_SAFE(N)                                                                         \
-  do {                                                                                       \
-    const int rc_ = jamd_reserve_dyn_lds((const void *)gmm_safe_kernel<DT, N>, dyn, "gprune safe"); \
-    if (rc_ != JAMD_OK) return rc_;                                                          \
-    hipLaunchKernelGGL((gmm_safe_kernel<DT, N>), grid, dim3(64 * kWaves), dyn, st, g->d_rec, \
-                       g->d_st_off_plain, frames, g->eng->d_addlog, out, T, g->S, g->D, g->rec, \
-                       cap, nsb, g->eng->addmin_f);                                          \
-  } while (0)
-  if (cap <= 2) JAMD_SAFE(2);
-  else if (cap <= 4) JAMD_SAFE(4);
-  else if (cap <= 8) JAMD_SAFE(8);
-  else if (cap <= 16) JAMD_SAFE(16);
-  else if (cap <= 32) JAMD_SAFE(32);
-  else JAMD_SAFE(64);
-#undef JAMD_SAFE
+  const int rc = dispatch_topn<2>(cap, [&](auto n) {
+    constexpr int N = decltype(n)::value;
+    const int rc = jamd_reserve_dyn_lds((const void *)gmm_safe_kernel<DT, N>, dyn, "gprune safe");
+    if (rc != JAMD_OK) return rc;
+    hipLaunchKernelGGL((gmm_safe_kernel<DT, N>), grid, dim3(64 * kWaves), dyn, st, g->d_rec,
+                       g->d_st_off_plain, frames, g->eng->d_addlog, out, T, g->S, g->D, g->rec,
+                       cap, nsb, g->eng->addmin_f);
+    return JAMD_OK;
+  });
+  if (rc != JAMD_OK) return rc;
   snprintf(g->last_kernel, sizeof(g->last_kernel), "gmm_safe<DT=%d> cap=%d", DT, cap);
   return JAMD_OK;
 }
@@ -388,48 +358,30 @@ int launch_book(jamd_gmm *g, const float *frames, int T, float *c_score, int *c_
   const dim3 grid(nfb, g->nbook);
   const size_t dyn = DT > 0 ? 0 : sizeof(float) * kWaves * g->D * 128;
   const int cap = g->tm_cap;
-#define JAMD_BOOK(N)                                                                          \
-  do {                                                                                        \
-    const int rc_ = jamd_reserve_dyn_lds((const void *)tmix_book_kernel<DT, N>, dyn, "tied-mixture codebooks"); \
-    if (rc_ != JAMD_OK) return rc_;                                                           \
-    hipLaunchKernelGGL((tmix_book_kernel<DT, N>), grid, dim3(64 * kWaves), dyn, st, g->d_book_rec, \
-                       g->d_book_off, frames, c_score, c_id, c_num, T, g->nbook, g->D, g->rec, cap); \
-  } while (0)
-  if (g->gprune == JAMD_GPRUNE_NONE) JAMD_BOOK(0);
-  else if (cap <= 2) JAMD_BOOK(2);
-  else if (cap <= 4) JAMD_BOOK(4);
-  else if (cap <= 8) JAMD_BOOK(8);
-  else if (cap <= 16) JAMD_BOOK(16);
-  else if (cap <= 32) JAMD_BOOK(32);
-  else JAMD_BOOK(64);
-#undef JAMD_BOOK
-  return JAMD_OK;
+  auto launch = [&](auto n) {
+    constexpr int N = decltype(n)::value;
+    const int rc = jamd_reserve_dyn_lds((const void *)tmix_book_kernel<DT, N>, dyn, "tied-mixture codebooks");
+    if (rc != JAMD_OK) return rc;
+    hipLaunchKernelGGL((tmix_book_kernel<DT, N>), grid, dim3(64 * kWaves), dyn, st, g->d_book_rec,
+                       g->d_book_off, frames, c_score, c_id, c_num, T, g->nbook, g->D, g->rec, cap);
+    return JAMD_OK;
+  };
+  if (g->gprune == JAMD_GPRUNE_NONE) return launch(std::integral_constant<int, 0>{});
+  return dispatch_topn<2>(cap, launch);
 }
 
 }  // namespace
 
-// entry points used by gmm_outprob.hip
+// entry points used by gmm_api.hip
 int jamd_gmm_launch_safe(jamd_gmm *g, const float *frames, int T, float *out, hipStream_t st) {
-  switch (g->D) {
-    case 39: return launch_safe<39>(g, frames, T, out, st);
-    case 38: return launch_safe<38>(g, frames, T, out, st);
-    case 26: return launch_safe<26>(g, frames, T, out, st);
-    case 25: return launch_safe<25>(g, frames, T, out, st);
-    default: return launch_safe<0>(g, frames, T, out, st);
-  }
+  return dispatch_veclen(g->D, [&](auto dt) { return launch_safe<decltype(dt)::value>(g, frames, T, out, st); });
 }
 
 int jamd_gmm_launch_tmix(jamd_gmm *g, const float *frames, int T, float *out, float *c_score,
                          int *c_id, int *c_num, hipStream_t st) {
   int rc;
   if (g->hist_method != 0) rc = launch_book_hist(g, frames, c_score, c_id, c_num, st);
-  else switch (g->D) {
-    case 39: rc = launch_book<39>(g, frames, T, c_score, c_id, c_num, st); break;
-    case 38: rc = launch_book<38>(g, frames, T, c_score, c_id, c_num, st); break;
-    case 26: rc = launch_book<26>(g, frames, T, c_score, c_id, c_num, st); break;
-    case 25: rc = launch_book<25>(g, frames, T, c_score, c_id, c_num, st); break;
-    default: rc = launch_book<0>(g, frames, T, c_score, c_id, c_num, st); break;
-  }
+  else rc = dispatch_veclen(g->D, [&](auto dt) { return launch_book<decltype(dt)::value>(g, frames, T, c_score, c_id, c_num, st); });
   if (rc != JAMD_OK || !out) return rc;
   const dim3 grid((g->ntied + 255) / 256, T < 4096 ? T : 4096);
   hipLaunchKernelGGL(tmix_state_kernel, grid, dim3(256), 0, st, g->d_tied_states, g->ntied,

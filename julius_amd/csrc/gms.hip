@@ -27,7 +27,7 @@ struct jamd_gms {
   int *d_st_off = nullptr;         // [Sgs + 1]
   float *d_logw = nullptr;         // [Egs]
   int *d_state2gs = nullptr;       // [S]
-  int *d_utt_off = nullptr; int utt_cap = 0;
+  int *d_utt_off = nullptr; size_t utt_bytes = 0;
   float *d_dens = nullptr; size_t dens_cap = 0;
   float *d_fs = nullptr; size_t fs_cap = 0;
 };
@@ -38,21 +38,15 @@ using namespace jamd;
 typedef __attribute__((address_space(3))) void lds_void;
 typedef const __attribute__((address_space(1))) void glb_void;
 
-__device__ __forceinline__ void wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 // One wave per utterance.  LDS: fs[Sgs] | idx[Sgs] | last[Sgs] | st_off[Sgs+1] | logw[Egs] | row[2][EgsPad].
 // The frame's per-Gaussian scores (one row of dens) arrive by LDS-DMA, the next frame's row while
 // this one is processed, so the serial walk over the frames never waits for HBM.
 // STRICT: lane 0 runs the reference's heap.  Otherwise every lane ranks its own states against all
 // (broadcast reads), which selects the same set unless two states tie exactly on the boundary; then
 // the lower state id wins where the reference's answer depends on the heap's history.
-// VAR 1 (the form that is launched; VAR 0 is the scalar ranking loop it replaced, 9.2 vs 7.3 ms): the two latency chains of the default
-// form -- one LDS read per ranking step, one per Gaussian in the max -- are batched four wide.
-template <bool STRICT, int VAR>
+// The two latency chains of the default form -- one LDS read per ranking step, one per Gaussian in the max -- are
+// batched four wide (7.3 ms against 9.2 ms for one read at a time, profiles/r02a_gms_timing_variants.json).
+template <bool STRICT>
 __global__ void __launch_bounds__(64)
 gms_select_kernel(const float *__restrict__ dens, const int *__restrict__ g_st_off, const float *__restrict__ g_logw,
                   const int *__restrict__ utt_off, float *__restrict__ fs_out, int Sgs, int Egs, int EgsPad, int nbest) {
@@ -90,24 +84,17 @@ gms_select_kernel(const float *__restrict__ dens, const int *__restrict__ g_st_o
       float maxprob = row[e0 + first];
       if (maxprob < JAMD_LOG_ZERO) maxprob = JAMD_LOG_ZERO;
       int maxi = first;
-      if constexpr (VAR == 1) {
-        int k = n - 1;
-        for (; k >= 3; k -= 4) {                                     // same visiting order, four loads in flight
-          const float p0 = row[e0 + k], p1 = row[e0 + k - 1], p2 = row[e0 + k - 2], p3 = row[e0 + k - 3];
-          if (k != first && p0 > maxprob) { maxprob = p0; maxi = k; }
-          if (k - 1 != first && p1 > maxprob) { maxprob = p1; maxi = k - 1; }
-          if (k - 2 != first && p2 > maxprob) { maxprob = p2; maxi = k - 2; }
-          if (k - 3 != first && p3 > maxprob) { maxprob = p3; maxi = k - 3; }
-        }
-        for (; k >= 0; k--) {
-          const float p = row[e0 + k];
-          if (k != first && p > maxprob) { maxprob = p; maxi = k; }
-        }
-      } else {
-        for (int k = n - 1; k >= 0; k--) {
-          const float p = row[e0 + k];
-          if (k != first && p > maxprob) { maxprob = p; maxi = k; }
-        }
+      int k = n - 1;
+      for (; k >= 3; k -= 4) {                                       // same visiting order, four loads in flight
+        const float p0 = row[e0 + k], p1 = row[e0 + k - 1], p2 = row[e0 + k - 2], p3 = row[e0 + k - 3];
+        if (k != first && p0 > maxprob) { maxprob = p0; maxi = k; }
+        if (k - 1 != first && p1 > maxprob) { maxprob = p1; maxi = k - 1; }
+        if (k - 2 != first && p2 > maxprob) { maxprob = p2; maxi = k - 2; }
+        if (k - 3 != first && p3 > maxprob) { maxprob = p3; maxi = k - 3; }
+      }
+      for (; k >= 0; k--) {
+        const float p = row[e0 + k];
+        if (k != first && p > maxprob) { maxprob = p; maxi = k; }
       }
       last[i] = maxi;
       float sum = 0.0f;
@@ -152,25 +139,18 @@ gms_select_kernel(const float *__restrict__ dens, const int *__restrict__ g_st_o
       for (int i = lane; i < Sgs; i += 64) {                        // rank of state i among all
         const float v = fs[i];
         int rank = 0;
-        if constexpr (VAR == 1) {
-          const float4 *f4 = reinterpret_cast<const float4 *>(fs);       // fs sits at LDS offset 0
-          int j = 0;
-          for (; j + 4 <= Sgs; j += 4) {
-            const float4 w = f4[j >> 2];
-            rank += (w.x > v || (w.x == v && j < i)) ? 1 : 0;
-            rank += (w.y > v || (w.y == v && j + 1 < i)) ? 1 : 0;
-            rank += (w.z > v || (w.z == v && j + 2 < i)) ? 1 : 0;
-            rank += (w.w > v || (w.w == v && j + 3 < i)) ? 1 : 0;
-          }
-          for (; j < Sgs; j++) {
-            const float w = fs[j];
-            rank += (w > v || (w == v && j < i)) ? 1 : 0;
-          }
-        } else {
-          for (int j = 0; j < Sgs; j++) {
-            const float w = fs[j];
-            rank += (w > v || (w == v && j < i)) ? 1 : 0;
-          }
+        const float4 *f4 = reinterpret_cast<const float4 *>(fs);         // fs sits at LDS offset 0
+        int j = 0;
+        for (; j + 4 <= Sgs; j += 4) {
+          const float4 w = f4[j >> 2];
+          rank += (w.x > v || (w.x == v && j < i)) ? 1 : 0;
+          rank += (w.y > v || (w.y == v && j + 1 < i)) ? 1 : 0;
+          rank += (w.z > v || (w.z == v && j + 2 < i)) ? 1 : 0;
+          rank += (w.w > v || (w.w == v && j + 3 < i)) ? 1 : 0;
+        }
+        for (; j < Sgs; j++) {
+          const float w = fs[j];
+          rank += (w > v || (w == v && j < i)) ? 1 : 0;
         }
         fs_out[(size_t)t * Sgs + i] = rank < nbest ? JAMD_LOG_ZERO : v;
       }
@@ -190,15 +170,6 @@ gms_combine_kernel(const float *__restrict__ fs, const int *__restrict__ state2g
     const float f = fs[(size_t)t * Sgs + g];
     if (f != JAMD_LOG_ZERO) scores[(size_t)t * S + s] = f;
   }
-}
-
-int grow(float **p, size_t *cap, size_t need) {
-  if (*cap >= need) return JAMD_OK;
-  if (*p) JAMD_HIP(hipFree(*p));
-  *p = nullptr; *cap = 0;
-  JAMD_HIP(hipMalloc(p, need));
-  *cap = need;
-  return JAMD_OK;
 }
 
 }  // namespace
@@ -258,22 +229,15 @@ int jamd_gms_apply_dev(jamd_gms *m, const float *dev_frames, int T, const int *u
   if (!utt_off) { utt_off = one; nutt = 1; }
   if (utt_off[0] != 0 || utt_off[nutt] != T) { jamd_set_error("jamd_gms_apply_dev: utt_off must run from 0 to T"); return JAMD_EINVAL; }
   int rc;
-  if (nutt + 1 > m->utt_cap) {
-    if (m->d_utt_off) JAMD_HIP(hipFree(m->d_utt_off));
-    m->d_utt_off = nullptr;
-    JAMD_HIP(hipMalloc(&m->d_utt_off, sizeof(int) * (nutt + 1)));
-    m->utt_cap = nutt + 1;
-  }
-  if ((rc = grow(&m->d_dens, &m->dens_cap, sizeof(float) * ((size_t)T * m->Egs + 64))) != JAMD_OK) return rc;
-  if ((rc = grow(&m->d_fs, &m->fs_cap, sizeof(float) * (size_t)T * m->Sgs)) != JAMD_OK) return rc;
+  if ((rc = jamd_grow(&m->d_utt_off, &m->utt_bytes, sizeof(int) * ((size_t)nutt + 1))) != JAMD_OK) return rc;
+  if ((rc = jamd_grow(&m->d_dens, &m->dens_cap, sizeof(float) * ((size_t)T * m->Egs + 64))) != JAMD_OK) return rc;
+  if ((rc = jamd_grow(&m->d_fs, &m->fs_cap, sizeof(float) * (size_t)T * m->Sgs)) != JAMD_OK) return rc;
   JAMD_HIP(hipMemcpyAsync(m->d_utt_off, utt_off, sizeof(int) * (nutt + 1), hipMemcpyHostToDevice, st));
   if ((rc = jamd_gmm_dens_dev(m->gs, dev_frames, T, m->d_dens, st)) != JAMD_OK) return rc;
   const int EgsPad = (m->Egs + 63) & ~63;
   const size_t lds = sizeof(float) * ((size_t)3 * m->Sgs + m->Sgs + 1 + m->Egs + 64 + 2 * (size_t)EgsPad);
   if (lds > 159 * 1024) { jamd_set_error("jamd_gms_apply_dev: a selection model of %d states / %d Gaussians does not fit in LDS", m->Sgs, m->Egs); return JAMD_EINVAL; }
-  // the four-wide ranking loop (template argument 1) measured 7.3 ms against 9.2 ms for the scalar one
-  // (profiles/r02a_gms_timing_variants.json) and is the only form launched
-  auto kern = m->strict ? gms_select_kernel<true, 1> : gms_select_kernel<false, 1>;
+  auto kern = m->strict ? gms_select_kernel<true> : gms_select_kernel<false>;
   if (lds > 48 * 1024) JAMD_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   hipLaunchKernelGGL(kern, dim3(nutt), dim3(64), lds, st, m->d_dens, m->d_st_off, m->d_logw, m->d_utt_off,
                      m->d_fs, m->Sgs, m->Egs, EgsPad, m->nbest);

@@ -12,7 +12,7 @@
 // The work is tiny (T x a few models x tens of Gaussians) and HBM-trivial; what matters is that it is
 // the reference's number.  One thread per (frame, model); the running sums of an utterance are float
 // additions in frame order (gmm.c:599), one thread per (utterance, model).
-#include "jamd_device.h"
+#include "gmm_dev.h"
 
 #include <cmath>
 #include <string>
@@ -23,7 +23,7 @@ struct jamd_rejgmm {
   int D = 0, nmodel = 0, gprune_num = 0, maxmix = 0;
   float *d_mean = nullptr, *d_ivar = nullptr, *d_gconst = nullptr, *d_logw = nullptr;
   int *d_st_off = nullptr, *d_ent_dens = nullptr, *d_model_state = nullptr;
-  int *d_utt_off = nullptr; int utt_cap = 0;
+  int *d_utt_off = nullptr; size_t utt_bytes = 0;
   std::vector<std::string> names;          // model names / is_voice: only known when loaded from a file
   std::vector<unsigned char> is_voice;
 };
@@ -181,16 +181,12 @@ int jamd_rejgmm_frame_scores_dev(jamd_rejgmm *m, const float *dev_frames, int T,
   const long total = (long)T * m->nmodel;
   const dim3 grid((unsigned)((total + 255) / 256));
   const int need = m->gprune_num < m->maxmix ? m->gprune_num : m->maxmix;
-#define JAMD_REJ(N)                                                                                      \
-  hipLaunchKernelGGL((rejgmm_frame_kernel<N>), grid, dim3(256), 0, st, m->d_mean, m->d_ivar, m->d_gconst, \
-                     m->d_st_off, m->d_ent_dens, m->d_logw, m->d_model_state, dev_frames, m->eng->d_addlog, \
-                     dev_out, T, m->nmodel, m->D, m->gprune_num, m->eng->addmin_f)
-  if (need <= 4) JAMD_REJ(4);
-  else if (need <= 8) JAMD_REJ(8);
-  else if (need <= 16) JAMD_REJ(16);
-  else if (need <= 32) JAMD_REJ(32);
-  else JAMD_REJ(64);
-#undef JAMD_REJ
+  dispatch_topn<4>(need, [&](auto n) {
+    hipLaunchKernelGGL((rejgmm_frame_kernel<decltype(n)::value>), grid, dim3(256), 0, st, m->d_mean, m->d_ivar, m->d_gconst,
+                       m->d_st_off, m->d_ent_dens, m->d_logw, m->d_model_state, dev_frames, m->eng->d_addlog,
+                       dev_out, T, m->nmodel, m->D, m->gprune_num, m->eng->addmin_f);
+    return JAMD_OK;
+  });
   hipError_t le = hipGetLastError();
   if (le != hipSuccess) { jamd_set_error("jamd_rejgmm_frame_scores_dev: launch failed: %s", hipGetErrorString(le)); return JAMD_ELAUNCH; }
   return JAMD_OK;
@@ -202,12 +198,8 @@ int jamd_rejgmm_utt_scores_dev(jamd_rejgmm *m, const float *dev_frame_scores, in
   if (utt_off[0] != 0 || utt_off[nutt] != T) { jamd_set_error("jamd_rejgmm_utt_scores_dev: utt_off must run from 0 to T"); return JAMD_EINVAL; }
   JAMD_HIP(hipSetDevice(m->eng->device));
   hipStream_t st = jamd_stream(m->eng, stream);
-  if (nutt + 1 > m->utt_cap) {
-    if (m->d_utt_off) JAMD_HIP(hipFree(m->d_utt_off));
-    m->d_utt_off = nullptr; m->utt_cap = 0;
-    JAMD_HIP(hipMalloc(&m->d_utt_off, sizeof(int) * (nutt + 1)));
-    m->utt_cap = nutt + 1;
-  }
+  const int rc = jamd_grow(&m->d_utt_off, &m->utt_bytes, sizeof(int) * ((size_t)nutt + 1));
+  if (rc != JAMD_OK) return rc;
   JAMD_HIP(hipMemcpyAsync(m->d_utt_off, utt_off, sizeof(int) * (nutt + 1), hipMemcpyHostToDevice, st));
   hipLaunchKernelGGL(rejgmm_sum_kernel, dim3((nutt * m->nmodel + 63) / 64), dim3(64), 0, st, dev_frame_scores,
                      m->d_utt_off, dev_out, nutt, m->nmodel);

@@ -308,6 +308,22 @@ def test_compound_model(engine, oracle):
         assert np.array_equal(gm.outprob_host(fr), oracle.gmm_outprob(mix, fr, code, n))
 
 
+def test_compound_model_with_empty_plain_states(engine, oracle):
+    """Tied-mixture states plus plain states that have no mixture entry at all (E_plain == 0, ntied < S): the log-sum
+    of no terms is LOG_ZERO (calc_mix.c:63-80).  A 25-frame call is short enough for the narrow form of K1, which has
+    no entry to give a lane: such a model stays with the tile kernel, as the 300-frame call does."""
+    m = synth.make_tied_gmm(S=12, nbook=2, K=24, D=39, seed=9)
+    mix = dict(m, st_off=np.concatenate([m["st_off"], np.repeat(m["st_off"][-1:], 3)]).astype(np.int32),
+               st_book=np.concatenate([m["st_book"], -np.ones(3, np.int32)]).astype(np.int32))
+    gm = lib.Gmm(engine, mix, gprune=lib.GPRUNE_NONE)
+    for T in (25, 300):
+        fr = synth.make_frames(m, T=T, seed=4, noise=2.0)
+        got = gm.outprob_host(fr)
+        want = oracle.gmm_outprob(mix, fr, lib.GPRUNE_NONE, 0)
+        assert np.all(want[:, 12:] == np.float32(-1000000.0))
+        assert np.array_equal(got, want), T
+
+
 @pytest.mark.parametrize("meth,code", [("max", lib.IWCD_MAX), ("avg", lib.IWCD_AVG), ("nbest", lib.IWCD_NBEST)])
 def test_golden_cdset(engine, meth, code):
     g = load("cdset.npz")

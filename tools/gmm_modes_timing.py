@@ -22,6 +22,7 @@ def run(name, model, gprune, n):
     print(f"{name}: S={gm.S} T={T}: {dt*1e3:.2f} ms -> {T/dt:.3e} frames/s, {T*gm.S/dt:.3e} frame*states/s [{gm.last_kernel()}]")
 m = synth.make_gmm(S=3000, M=16, D=39, seed=0)
 run("plain none", m, lib.GPRUNE_NONE, 0)
+run("plain none, generic D=24", synth.make_gmm(S=3000, M=16, D=24, seed=0), lib.GPRUNE_NONE, 0)
 run("plain safe N=2", m, lib.GPRUNE_SAFE, 2)
 run("plain safe N=8", m, lib.GPRUNE_SAFE, 8)
 tm = synth.make_tied_gmm(S=3000, nbook=129, K=64, D=39, seed=1)

@@ -11,7 +11,12 @@ instruction text (addresses and encodings stripped); it lists what differs and e
 The exact-order first-pass kernels (--filter beam_exact, --filter prune_order) are all compiled by csrc/beam_exact.hip, from
 beam_exact_dev.h, beam_prune.h, beam_sweep.h and beam_exact_mp.h.  A call of a function that is not inlined is encoded
 relative to the call site, so moving a kernel to another unit -- or changing the order of the kernels in one -- changes its
-text here even when nothing else does."""
+text here even when nothing else does.
+
+The scoring kernels (--filter gmm_, --filter tmix_, --filter rejgmm, --filter gms_): csrc/gmm_outprob.hip compiles K1
+(gmm_tile_kernel), its generic-D and narrow forms and gmm_dens_kernel, csrc/gmm_pruned.hip K1s (gmm_safe_kernel), K2 and
+K2h (tmix_*), both from gmm_dev.h and jamd_device.h; csrc/rejgmm.hip (gmm_dev.h's top-N list) and csrc/gms.hip hold their
+own.  csrc/gmm_api.hip, the host layer, contains no kernel."""
 import argparse
 import hashlib
 import json
