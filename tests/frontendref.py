@@ -47,6 +47,57 @@ class CMNWork(C.Structure):
                 ("do_map", C.c_ubyte), ("static_cvn_only", C.c_ubyte)]
 
 
+def same(a, b):
+    """Bits for numbers, NaN for NaN (the payload differs by architecture)."""
+    a, b = np.ascontiguousarray(a, np.float32), np.ascontiguousarray(b, np.float32)
+    if a.shape != b.shape:
+        return False
+    na, nb = np.isnan(a), np.isnan(b)
+    return bool(np.array_equal(na, nb) and np.array_equal(a.view(np.uint32)[~na], b.view(np.uint32)[~nb]))
+
+
+def first_diff(a, b):
+    bad = np.argwhere(~((a.view(np.uint32) == b.view(np.uint32)) | (np.isnan(a) & np.isnan(b))))
+    if len(bad) == 0:
+        return "shape" if a.shape != b.shape else "none"
+    t, d = bad[0]
+    return f"{len(bad)} values differ, first at frame {t} dim {d}: device {a[t, d]!r} reference {b[t, d]!r}"
+
+
+# Geometries away from the speech defaults, where the frame kernel's 64-lane loops and the tables change
+# path (tests/test_frontend_edges_gpu.py; the ones that change a table also in tests/test_frontend_host.py):
+# name -> (kind, vecsize, fields on top of the defaults)
+EDGE_GEOMETRY = {
+    "fs512": ("MFCC_E_D_A_Z", 39, dict(framesize=512, frameshift=160)),          # window == fftN: no zero padding
+    "fs256": ("MFCC_E_D_A_Z", 39, dict(framesize=256, frameshift=100)),
+    "fs257": ("MFCC_E_D_A_Z", 39, dict(framesize=257, frameshift=100)),          # fftN / 2 + 1: maximal padding
+    "fs2049": ("MFCC_E_D_N_Z", 25, dict(framesize=2049, frameshift=512)),        # two frames per workgroup
+    "fs4096": ("MFCC_E_D_N_Z", 25, dict(framesize=4096, frameshift=1024)),       # the limit
+    "fs16": ("MFCC_E_D_A_Z", 39, dict(framesize=16, frameshift=8)),              # fftN 16, nv2 8: lanes without work
+    "fs16_fb4": ("MFCC_E_D_A", 9, dict(framesize=16, frameshift=8, fbank_num=4)),
+    "fs33": ("MFCC_E_D_A_Z", 39, dict(framesize=33, frameshift=16)),             # fftN 64, nv2 32
+    "fs64": ("MFCC_E_D_A_Z", 39, dict(framesize=64, frameshift=32)),             # fftN == 64
+    "fs128_fb12": ("MFCC_E_D_A_Z", 39, dict(framesize=128, frameshift=64, fbank_num=12)),   # nv2 == 64
+    "gap": ("MFCC_E_D_A_Z", 39, dict(framesize=400, frameshift=640)),            # samples between frames unread
+    "fbank65": ("FBANK_D_A_Z", 195, dict(fbank_num=65)),                         # second trip of the bin loop
+    "fbank80": ("FBANK_D_A", 240, dict(fbank_num=80)),
+    "melspec128": ("MELSPEC", 128, dict(fbank_num=128, usepower=1)),
+    "mfcc100ch": ("MFCC_E_D_A_Z", 39, dict(fbank_num=100)),                      # DCT over > 64 channels
+    "mfcc20": ("MFCC_E_D_A_Z", 63, dict(fbank_num=40)),                          # 20 cepstra
+    "mfcc_plain": ("MFCC", 12, {}),
+    "mfcc_0_only": ("MFCC_0", 13, {}),
+    "mfcc_e_0_n": ("MFCC_E_0_D_N_Z", 27, {}),
+    "band_clamps": ("MFCC_E_D_A_Z", 39, dict(lopass=0, hipass=9000)),            # klo < 2 -> 2, khi > nv2 -> nv2
+    "narrow_band": ("MFCC_E_D_A_Z", 39, dict(lopass=1000, hipass=2000)),         # channels with one FFT bin or none
+    "vtln_lt1": ("MFCC_E_D_A_Z", 39, dict(vtln_alpha=0.9, vtln_lower=300.0, vtln_upper=6000.0)),
+    "fbank_power": ("FBANK_D_A_Z", 72, dict(usepower=1, zmeanframe=1)),
+    "zmean_rawe": ("MFCC_E_D_A_Z", 39, dict(zmeanframe=1, raw_e=1, enormal=1)),
+}
+# the ones whose tables differ from what tests/test_frontend_host.py already holds to WMP_work_new()
+EDGE_TABLES = ("fs16", "fs16_fb4", "fs33", "fs64", "fs512", "fs4096", "fbank80", "melspec128", "mfcc100ch", "mfcc20",
+               "band_clamps", "narrow_band")
+
+
 # the Value fields make_default_para() and calc_para_from_header() set, by jamd_frontend_desc name
 DESC_FIELDS = ("smp_period", "smp_freq", "framesize", "frameshift", "preEmph", "lifter", "fbank_num", "delWin",
                "accWin", "silFloor", "escale", "hipass", "lopass", "enormal", "raw_e", "zmeanframe", "usepower", "cvn",
@@ -93,6 +144,13 @@ class RefFrontend:
         rows = np.zeros((T, max(v.vecbuflen, v.veclen) + 4), np.float32)
         ptrs = (P(cf) * T)(*[r.ctypes.data_as(P(cf)) for r in rows])
         w = self.work(v)
+        # Wav2MFCC() copies framesize + 1 samples into bf[1 .. framesize + 1] (wav2mfcc-buffer.c:78-80), but
+        # WMP_work_new() sizes bf at fftN floats (mfcc-core.c:665): at framesize >= fftN - 1 the reference writes
+        # past its own buffer.  It reads bf[1 .. framesize] only, so lending it a buffer with room changes no
+        # value; keep this swap, or the windows that are a power of two are undefined behaviour
+        own = C.cast(w.contents.bf, vp).value
+        room = np.zeros(w.contents.fb.fftN + 2, np.float32)
+        w.contents.bf = room.ctypes.data_as(P(cf))
         cw = None
         keep = []
         if cmean is not None:
@@ -107,6 +165,7 @@ class RefFrontend:
         t0 = time.perf_counter()
         got = self.lib.Wav2MFCC(buf.ctypes.data, ptrs, C.byref(v), n, w, C.addressof(cw) if cw is not None else None)
         self.last_s = time.perf_counter() - t0      # the reference's own call alone (tools/frontend_timing.py)
+        w.contents.bf = C.cast(own, P(cf))
         self.lib.WMP_free(w)
         assert got == T
         feat = rows[:, :v.veclen]

@@ -10,7 +10,7 @@ import numpy as np
 import pytest
 
 from julius_amd import lib, synth
-from frontendref import RefFrontend
+from frontendref import RefFrontend, first_diff, same
 
 pytestmark = pytest.mark.gpu
 
@@ -18,22 +18,6 @@ pytestmark = pytest.mark.gpu
 @pytest.fixture(scope="module")
 def rf(ref):
     return RefFrontend(ref)
-
-
-def same(a, b):
-    a, b = np.ascontiguousarray(a, np.float32), np.ascontiguousarray(b, np.float32)
-    if a.shape != b.shape:
-        return False
-    na, nb = np.isnan(a), np.isnan(b)
-    return bool(np.array_equal(na, nb) and np.array_equal(a.view(np.uint32)[~na], b.view(np.uint32)[~nb]))
-
-
-def first_diff(a, b):
-    bad = np.argwhere(~((a.view(np.uint32) == b.view(np.uint32)) | (np.isnan(a) & np.isnan(b))))
-    if len(bad) == 0:
-        return "shape" if a.shape != b.shape else "none"
-    t, d = bad[0]
-    return f"{len(bad)} values differ, first at frame {t} dim {d}: device {a[t, d]!r} reference {b[t, d]!r}"
 
 
 # (name, kind, vecsize, fields, extra) -- extra: splice, cmean / cvar generation, static_cvn_only

@@ -6,7 +6,7 @@ import numpy as np
 import pytest
 
 from julius_amd import lib
-from frontendref import DESC_FIELDS, RefFrontend
+from frontendref import DESC_FIELDS, EDGE_GEOMETRY, EDGE_TABLES, RefFrontend
 
 KINDS = [("MFCC_E_D_A_Z", 39), ("MFCC_E_D_N_Z", 25), ("MFCC_E_D_A", 39), ("MFCC_0_D_A_Z", 39), ("MFCC_E_Z", 13),
          ("MFCC_0_E_D_A", 42), ("MFCC_E_D_A_Z", 36), ("FBANK_D_A_Z", 72), ("MELSPEC", 24), ("FBANK", 40),
@@ -98,7 +98,7 @@ TABLE_CASES = [
     ("MFCC_E_D_A_Z", 39, dict(smp_period=1250, smp_freq=8000, framesize=200, frameshift=80, fbank_num=20)),
     ("FBANK_D_A_Z", 72, {}),
     ("MELSPEC", 24, dict(usepower=1)),
-]
+] + [EDGE_GEOMETRY[k] for k in EDGE_TABLES]   # windows of 16 .. 4096 samples, 4 .. 128 channels, 20 cepstra, clamped bands
 
 
 @pytest.mark.parametrize("kind,vecsize,fields", TABLE_CASES)
