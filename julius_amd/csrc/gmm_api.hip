@@ -112,6 +112,22 @@ static int gmm_create_impl(jamd_engine *e, const jamd_gmm_desc *d, int gprune, i
   }
   JAMD_HIP(hipMalloc(&g->d_rec, sizeof(float) * (rec.size() ? rec.size() : 4)));
   JAMD_HIP(hipMemcpy(g->d_rec, rec.data(), sizeof(float) * rec.size(), hipMemcpyHostToDevice));
+  if (D == 39) {
+    // the same records once more in the order K1's record ring loads them (jamd_gmm::d_rec_ring, gmm_host.h): packed
+    // here, once per model -- 15.4 MB at 3000 states x 16 mixtures
+    constexpr int kRing = 80;
+    std::vector<float> ring((size_t)g->E_plain * kRing, 0.0f);
+    for (int en = 0; en < g->E_plain; en++) {
+      const float *r = rec.data() + (size_t)en * g->rec;
+      float *q = ring.data() + (size_t)en * kRing;
+      q[0] = r[2 * D]; q[1] = r[2 * D + 1];
+      for (int k = 0; k < 7; k++) { q[2 + k] = r[k]; q[9 + k] = r[D + k]; }
+      for (int c = 1; c < 5; c++)
+        for (int k = 0; k < 8; k++) { q[16 * c + k] = r[8 * c - 1 + k]; q[16 * c + 8 + k] = r[D + 8 * c - 1 + k]; }
+    }
+    JAMD_HIP(hipMalloc(&g->d_rec_ring, sizeof(float) * (ring.size() ? ring.size() : 4)));
+    JAMD_HIP(hipMemcpy(g->d_rec_ring, ring.data(), sizeof(float) * ring.size(), hipMemcpyHostToDevice));
+  }
   JAMD_HIP(hipMalloc(&g->d_st_off, sizeof(int) * (g->S + 1)));
   JAMD_HIP(hipMemcpy(g->d_st_off, d->st_off, sizeof(int) * (g->S + 1), hipMemcpyHostToDevice));
   JAMD_HIP(hipMalloc(&g->d_st_off_plain, sizeof(int) * (g->S + 1)));
@@ -166,7 +182,7 @@ int jamd_gmm_create(jamd_engine *e, const jamd_gmm_desc *d, int gprune, int gpru
 void jamd_gmm_destroy(jamd_gmm *g) {
   if (!g) return;
   (void)hipSetDevice(g->eng->device);
-  void *ptrs[] = { g->d_rec, g->d_cur_utt_off, g->d_st_off, g->d_st_off_plain, g->d_tied_states, g->d_st_book, g->d_book_off, g->d_book_rec,
+  void *ptrs[] = { g->d_rec, g->d_rec_ring, g->d_cur_utt_off, g->d_st_off, g->d_st_off_plain, g->d_tied_states, g->d_st_book, g->d_book_off, g->d_book_rec,
                    g->d_ent_logw, g->d_frames, g->d_out, g->d_tm_score, g->d_tm_id, g->d_tm_num, g->d_narrow };
   for (void *p : ptrs) if (p) (void)hipFree(p);
   if (g->h_utt_off) (void)hipHostFree(g->h_utt_off);

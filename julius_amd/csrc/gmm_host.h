@@ -15,6 +15,9 @@ struct jamd_gmm {
   int maxmix = 0;
   // device model
   float *d_rec = nullptr;         // [E][rec]: mean[D], ivar[D], gconst, logw
+  float *d_rec_ring = nullptr;    // [E_plain][80], D = 39 only: the plain states' records again, in the order K1's record ring
+                                  //   loads them -- five 64-byte chunks: [gconst, logw, mean 0..6, ivar 0..6], then
+                                  //   [mean of 8 dims, ivar of the same 8 dims] for dims 7.., 15.., 23.., 31..38
   int *d_st_off = nullptr;        // [S+1] original entry offsets (index d_ent_logw)
   int *d_st_off_plain = nullptr;  // [S+1] offsets into d_rec; a tied-mixture state has an empty range
   int E_plain = 0;

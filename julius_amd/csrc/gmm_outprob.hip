@@ -156,6 +156,159 @@ gmm_tile_kernel(const float *__restrict__ rec, const int *__restrict__ st_off,
   }
 }
 
+// ---------------------------------------------------------------------------------------
+// K1 at D = 39 with the RECORD RING.  Same lanes, frames, arithmetic, log-sum, tile and epilogue as gmm_tile_kernel;
+// what differs is how a Gaussian's record reaches the SGPRs and the order in which the D-loop is written down.
+//
+// gmm_tile_kernel reads a record where it uses it: three s_load_dwordx16 at the top of a Gaussian and a wait in the
+// next instruction, two more chunks waited for 12 and 2 packed operations after they are issued -- about 2.5 scalar
+// load latencies per Gaussian that only the SIMD's other waves cover.  Here the records come from the chunk-ordered
+// copy jamd_gmm::d_rec_ring (80 floats in five 64-byte chunks, gmm_host.h) into a ring of three 16-SGPR homes that is
+// refilled in place ONE GAUSSIAN AHEAD; per Gaussian
+//     chunk 0 from home 0 | load this record's chunk 3 -> home 0
+//     chunk 1 from home 1 | load this record's chunk 4 -> home 1
+//     chunk 2 from home 2 | WAIT
+//     chunk 3 from home 0 | load the next record's chunks 0, 2 -> homes 0, 2
+//     chunk 4 from home 1 | load the next record's chunk 1 -> home 1
+//     log-sum step        | WAIT
+// two waits: the first 32 packed operations behind the youngest load it retires, the second 36 behind the next record's
+// chunks 0 and 2 and the log-sum step behind its chunk 1 (home 1 is free only once chunk 4 is used: three homes allow no
+// better, and the kernel's 104 SGPRs leave no room for a fourth).  The "next record" of a state's
+// first entry (the scan runs from the last mixture to the first) is the last entry of the block's next state; the
+// block's last state reads its own last entry again, and a state that finds another record in the homes than its last
+// (the first state of a block, the state after an empty one) loads it itself.
+//
+// The loads and waits are asm statements between sched_barrier(0)s: written as plain loads the scheduler sinks the
+// next record's loads to the top of the loop, which is gmm_tile_kernel's schedule again.  The compiler does not know
+// that an asm load's destination is written LATER than the statement, so it must be given no reason to touch a home
+// between a load into it and the wait that retires it.  The one thing it does of its own accord is to copy a home
+// (s_mov_b64 x 8) where control flow joins -- the loop's back edge, the end of an `if` --, and such a copy in front of
+// the wait moves registers the load has not written yet: a result that is wrong only sometimes.  Hence THE RULE OF
+// THIS KERNEL: every wait stands in the same basic block as the loads it retires, before any branch or join -- the
+// second wait is the last statement of the loop body, the prologue's wait is inside its `if` -- and no statement
+// between a load and its wait names the home.  profiles/gmm_ring_loop_isa.txt holds the loop of both instantiations as
+// compiled; check it again after any change here (no instruction between an s_load_dwordx16 and the next
+// s_waitcnt lgkmcnt(0) may name the load's destination registers).
+//
+// The D-loop is skewed by one stage per dimension inside each chunk: a step issues sub(i), sq(i-1), mul_ivar(i-2),
+// acc += (i-3), so every operand is three instructions old and the packed pipe is not held up by its own result.
+// The additions are still ONE chain in ascending d from gconst: the same float sequence as gauss_pair().
+typedef float f16v __attribute__((ext_vector_type(16)));
+constexpr int kRingRec = 80;       // floats per entry of d_rec_ring (gmm_api.hip packs it)
+
+template <int BYTE_OFF>
+__device__ __forceinline__ void ring_load(f16v &home, const float *chunks) {
+  __builtin_amdgcn_sched_barrier(0);
+  asm volatile("s_load_dwordx16 %0, %1, %2" : "=s"(home) : "s"(chunks), "i"(BYTE_OFF));
+  __builtin_amdgcn_sched_barrier(0);
+}
+__device__ __forceinline__ void ring_wait(f16v &h0, f16v &h1, f16v &h2) {
+  __builtin_amdgcn_sched_barrier(0);
+  asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(h0), "+s"(h1), "+s"(h2));
+  __builtin_amdgcn_sched_barrier(0);
+}
+// N dimensions of the D-loop from one home: means at h[MU0 ..], inverse variances at h[IV0 ..], frames v[0 .. N - 1]
+template <int N, int MU0, int IV0>
+__device__ __forceinline__ void ring_chunk(f2 &acc, const f2 *v, const f16v &h) {
+  f2 x[N], q[N], w[N];
+#pragma unroll
+  for (int i = 0; i < N + 3; i++) {
+    if (i < N) { const float mu = h[MU0 + i]; x[i] = v[i] - f2{mu, mu}; }
+    if (i >= 1 && i - 1 < N) q[i - 1] = x[i - 1] * x[i - 1];
+    if (i >= 2 && i - 2 < N) { const float iv = h[IV0 + i - 2]; w[i - 2] = q[i - 2] * f2{iv, iv}; }
+    if (i >= 3) acc = acc + w[i - 3];
+    __builtin_amdgcn_sched_barrier(0);
+  }
+}
+
+template <int NS, bool HAS_NULL>
+__global__ void __launch_bounds__(64 * kWaves)
+gmm_tile_ring_kernel(const float *__restrict__ ring, const int *__restrict__ st_off,
+                     const float *__restrict__ frames, const float *__restrict__ tbl,
+                     float *__restrict__ out, int T, int S, int nsb, int nfb, int nstb,
+                     float addmin_f) {
+  constexpr int D = 39, FPL = 2;
+  constexpr int FPW = 64 * FPL;
+  __shared__ float tile[kWaves][FPW][NS + 1];
+
+  int fb, sb;
+  if (!decode_block(nfb, nstb, fb, sb)) return;
+  const int lane = threadIdx.x & 63;
+  const int wave = threadIdx.x >> 6;
+  const int t0 = (fb * kWaves + wave) * FPW;
+  if (t0 >= T) return;  // whole wave out of range (no block-level barriers below)
+
+  f2 v[D];
+  load_frames<D>(v, nullptr, frames, t0, T, D, lane);
+
+  // (the addlog table as a raw buffer: see gmm_tile_kernel)
+  const __amdgpu_buffer_rsrc_t tbl_rsrc = __builtin_amdgcn_make_buffer_rsrc((void *)tbl, 0, 4 * (JAMD_TBLSIZE + 1), 0x00020000);
+  const float naddmin = -addmin_f;
+  const int s_begin = sb * nsb;
+  const int s_end = min(S, s_begin + nsb);
+  f16v h0, h1, h2;             // the ring: chunks 0 / 1 / 2 of record `held` at the top of a Gaussian
+  int held = -1;
+  for (int sg = s_begin; sg < s_end; sg += NS) {
+    const int ns = min(NS, s_end - sg);
+    for (int si = 0; si < ns; si++) {
+      const int s = sg + si;
+      const int e0 = st_off[s], e1 = st_off[s + 1];
+      // the record behind this state's first entry: the next state's last one (its own last one when that state is
+      // empty: a valid record, and `held` sends the state after it through the prologue), or this state's last again
+      const int e_over = (s + 1 < s_end ? st_off[s + 2] : e1) - 1;
+      f2 y2 = {JAMD_LOG_ZERO, JAMD_LOG_ZERO}, tv2 = {0.0f, 0.0f};   // running log-sum and pending table term
+      if (e1 > e0 && held != e1 - 1) {
+        const float *r = ring + (size_t)(e1 - 1) * kRingRec;
+        ring_load<0>(h0, r);
+        ring_load<64>(h1, r);
+        ring_load<128>(h2, r);
+        ring_wait(h0, h1, h2);     // inside the `if`: see the rule above
+      }
+      for (int e = e1 - 1; e >= e0; e--) {
+        const float *r = ring + (size_t)e * kRingRec;
+        const float *rn = ring + (size_t)(e > e0 ? e - 1 : e_over) * kRingRec;
+        const float gc = h0[0], lw = h0[1];
+        const bool nulld = HAS_NULL && (gc != gc);  // NULL density marker (gprune_none.c:67)
+        f2 acc = {gc, gc};
+        ring_chunk<7, 2, 9>(acc, v, h0);
+        ring_load<192>(h0, r);
+        ring_chunk<8, 0, 8>(acc, v + 7, h1);
+        ring_load<256>(h1, r);
+        ring_chunk<8, 0, 8>(acc, v + 15, h2);
+        ring_wait(h0, h1, h2);
+        ring_chunk<8, 0, 8>(acc, v + 23, h0);
+        ring_load<0>(h0, rn);
+        ring_load<128>(h2, rn);
+        ring_chunk<8, 0, 8>(acc, v + 31, h1);
+        ring_load<64>(h1, rn);
+        {
+          // the log-sum step of gmm_tile_kernel (see the notes there), for the lane's one frame pair
+          f2 s2 = acc * f2{-0.5f, -0.5f};
+          if (nulld) s2 = f2{JAMD_LOG_ZERO, JAMD_LOG_ZERO};
+          s2 = s2 + f2{lw, lw};
+          __builtin_amdgcn_sched_barrier(0);     // keep the wait for the gathered term behind the D-loop
+          const f2 yy = y2 + tv2;
+          const f2 hi = {__builtin_fmaxf(s2.x, yy.x), __builtin_fmaxf(s2.y, yy.y)};
+          const f2 df = s2 - yy;
+          const float a0 = __builtin_fabsf(df.x), a1 = __builtin_fabsf(df.y);
+          unsigned o0 = ((unsigned)((double)a0 * JAMD_TMAG + 0.5)) << 2, o1 = ((unsigned)((double)a1 * JAMD_TMAG + 0.5)) << 2;
+          o0 = (a0 <= naddmin) ? o0 : 4u * (unsigned)JAMD_TBLSIZE;
+          o1 = (a1 <= naddmin) ? o1 : 4u * (unsigned)JAMD_TBLSIZE;
+          tv2 = f2{__builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(tbl_rsrc, (int)o0, 0, 0)),
+                   __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(tbl_rsrc, (int)o1, 0, 0))};
+          y2 = hi;
+        }
+        ring_wait(h0, h1, h2);     // the last statement of the body: see the rule above
+      }
+      if (e1 > e0) held = e_over;
+      const f2 fin = y2 + tv2;
+      tile[wave][lane][si] = finish_state(fin.x);
+      tile[wave][64 + lane][si] = finish_state(fin.y);
+    }
+    store_tile<NS, FPW>(tile[wave], out, t0, T, S, sg, ns, lane);
+  }
+}
+
 // Generic-D variant: the frame vectors sit in LDS transposed [d][frame-in-wave] (load_frames<0>), a Gaussian is
 // gauss_pair<0> on the lane's two frames and the log-sum the plain in-lane addlog_step() in the same order; blocks,
 // tile and epilogue as above.
@@ -214,15 +367,28 @@ int launch_tile(jamd_gmm *g, const float *frames, int T, float *out, hipStream_t
   const int nsb = NS;
   const int nstb = (g->S + nsb - 1) / nsb;
   const int grid = xcd_grid(nstb, nfb);
-  if (g->has_null)
-    hipLaunchKernelGGL((gmm_tile_kernel<D, FPL, NS, true>), dim3(grid), dim3(64 * kWaves), 0, st,
-                       g->d_rec, g->d_st_off_plain, frames, g->eng->d_addlog, out, T, g->S, nsb, nfb,
-                       nstb, g->eng->addmin_f);
-  else
-    hipLaunchKernelGGL((gmm_tile_kernel<D, FPL, NS, false>), dim3(grid), dim3(64 * kWaves), 0, st,
-                       g->d_rec, g->d_st_off_plain, frames, g->eng->d_addlog, out, T, g->S, nsb, nfb,
-                       nstb, g->eng->addmin_f);
-  snprintf(g->last_kernel, sizeof(g->last_kernel), "gmm_tile<D=%d,FPL=%d,NS=%d> grid=%d nsb=%d", D, FPL, NS, grid, nsb);
+  if constexpr (D == 39 && FPL == 2) {
+    // the record-ring form of the kernel (above); the suffix keeps measurements taken on the other form apart
+    if (g->has_null)
+      hipLaunchKernelGGL((gmm_tile_ring_kernel<NS, true>), dim3(grid), dim3(64 * kWaves), 0, st,
+                         g->d_rec_ring, g->d_st_off_plain, frames, g->eng->d_addlog, out, T, g->S, nsb, nfb,
+                         nstb, g->eng->addmin_f);
+    else
+      hipLaunchKernelGGL((gmm_tile_ring_kernel<NS, false>), dim3(grid), dim3(64 * kWaves), 0, st,
+                         g->d_rec_ring, g->d_st_off_plain, frames, g->eng->d_addlog, out, T, g->S, nsb, nfb,
+                         nstb, g->eng->addmin_f);
+    snprintf(g->last_kernel, sizeof(g->last_kernel), "gmm_tile<D=%d,FPL=%d,NS=%d,ring> grid=%d nsb=%d", D, FPL, NS, grid, nsb);
+  } else {
+    if (g->has_null)
+      hipLaunchKernelGGL((gmm_tile_kernel<D, FPL, NS, true>), dim3(grid), dim3(64 * kWaves), 0, st,
+                         g->d_rec, g->d_st_off_plain, frames, g->eng->d_addlog, out, T, g->S, nsb, nfb,
+                         nstb, g->eng->addmin_f);
+    else
+      hipLaunchKernelGGL((gmm_tile_kernel<D, FPL, NS, false>), dim3(grid), dim3(64 * kWaves), 0, st,
+                         g->d_rec, g->d_st_off_plain, frames, g->eng->d_addlog, out, T, g->S, nsb, nfb,
+                         nstb, g->eng->addmin_f);
+    snprintf(g->last_kernel, sizeof(g->last_kernel), "gmm_tile<D=%d,FPL=%d,NS=%d> grid=%d nsb=%d", D, FPL, NS, grid, nsb);
+  }
   return JAMD_OK;
 }
 
