@@ -183,7 +183,7 @@ void jamd_gmm_destroy(jamd_gmm *g) {
   if (!g) return;
   (void)hipSetDevice(g->eng->device);
   void *ptrs[] = { g->d_rec, g->d_rec_ring, g->d_cur_utt_off, g->d_st_off, g->d_st_off_plain, g->d_tied_states, g->d_st_book, g->d_book_off, g->d_book_rec,
-                   g->d_ent_logw, g->d_frames, g->d_out, g->d_tm_score, g->d_tm_id, g->d_tm_num, g->d_narrow };
+                   g->d_ent_logw, g->d_frames, g->d_out, g->d_tm_score, g->d_tm_id, g->d_tm_num, g->d_tm_flag, g->d_narrow };
   for (void *p : ptrs) if (p) (void)hipFree(p);
   if (g->h_utt_off) (void)hipHostFree(g->h_utt_off);
   if (g->ev_utt_off) (void)hipEventDestroy(g->ev_utt_off);
@@ -252,7 +252,7 @@ int jamd_gmm_dens_host(jamd_gmm *g, const float *host_frames, int T, float *host
 
 // utterance boundaries of the running call, for the one scoring path that cares where an input begins
 static int set_utterances(jamd_gmm *g, const int *utt_off, int nutt, hipStream_t st) {
-  if (g->hist_method == 0) return JAMD_OK;
+  if (g->ntied == 0 || g->gprune == JAMD_GPRUNE_NONE) return JAMD_OK;   // (heu / beam arrive here as safe + hist_method)
   int rc;
   if ((rc = jamd_grow(&g->d_cur_utt_off, &g->utt_off_bytes, sizeof(int) * ((size_t)nutt + 1))) != JAMD_OK) return rc;
   // utt_off is the caller's memory: staged in a PINNED buffer the model owns, so that the copy is truly asynchronous (a

@@ -135,6 +135,33 @@ __device__ __forceinline__ void topn_push(float (&sc)[NMAX], int (&id)[NMAX], in
   if (len < cap) len++;
 }
 
+// gprune_safe() without history (gprune_safe.c:185-196; the same loop closes gprune_heu() and gprune_beam()): while the
+// list fills, a Gaussian is scored by compute_g_base(); once it is full, by compute_g_safe() (:76-97), which answers
+// LOG_ZERO for a Gaussian whose score lies below the list's last entry (its partial sums only grow, so the final sum
+// decides), and the caller drops what is not above that entry.  Normally that is the same as pushing the full score.
+// Not for a frame so far from every Gaussian that the kept scores lie below LOG_ZERO itself: there the LOG_ZERO the
+// reference got back IS above the last entry and enters the list as the Gaussian's score.
+template <int NMAX>
+__device__ __forceinline__ void topn_push_safe(float (&sc)[NMAX], int (&id)[NMAX], int &len, int cap,
+                                               float score, int gid) {
+  float last = score;             // value of sc[cap-1]
+#pragma unroll
+  for (int i = 0; i < NMAX; i++) if (i == cap - 1) last = sc[i];
+  if (len == cap && score < last) score = JAMD_LOG_ZERO;
+  topn_push<NMAX>(sc, id, len, cap, score, gid);
+}
+
+// Does the visiting order show in a list this score is pushed into?  It does where the score equals a kept one (which
+// of two equal Gaussians survives, and where it sits, follows the order) and where compute_g_safe()'s LOG_ZERO can enter
+// (above): some score at or below LOG_ZERO.  Without either the list is the N best scores whatever the order.
+template <int NMAX>
+__device__ __forceinline__ bool topn_order_shows(const float (&sc)[NMAX], int len, float score) {
+  bool shows = !(score > JAMD_LOG_ZERO);
+#pragma unroll
+  for (int i = 0; i < NMAX; i++) shows |= (i < len && sc[i] == score);
+  return shows;
+}
+
 // ... and the NMAX a list of `cap` entries is instantiated with: cap rounded up to LO, .., 16, 32, 64 (LO = 2 or 4).
 template <int LO, typename F>
 static inline int dispatch_topn(int cap, F &&f) {

@@ -33,14 +33,15 @@ struct jamd_gmm {
   int tm_cap = 0;                 // slots per (frame, book) in the codebook cache
   bool has_null = false;          // some mixture entry names no density (NULL density): K1 keeps its LOG_ZERO selects
   int hist_method = 0;            // JAMD_GPRUNE_HEU / _BEAM over tied-mixture codebooks (history pruning), else 0
-  int *d_cur_utt_off = nullptr;   // [cur_nutt + 1] utterance boundaries of the running call (history pruning restarts
-  int cur_nutt = 0; size_t utt_off_bytes = 0;   //   at every utterance's first frame)
+  int *d_cur_utt_off = nullptr;   // [cur_nutt + 1] utterance boundaries of the running call (a codebook's history -- heu / beam
+  int cur_nutt = 0; size_t utt_off_bytes = 0;   //   thresholds, safe's visiting order -- restarts at every utterance's first frame)
   // scratch
   float *d_frames = nullptr; size_t frames_cap = 0;
   float *d_out = nullptr; size_t out_cap = 0;
   float *d_tm_score = nullptr; int *d_tm_id = nullptr; int *d_tm_num = nullptr;
   float *d_narrow = nullptr; size_t narrow_cap = 0;   // [kNarrowT][E_plain] weighted Gaussian scores of a narrow call (K1n, gmm_outprob.hip)
   size_t tm_cap_bytes = 0, tm_id_bytes = 0, tm_num_bytes = 0;
+  int *d_tm_flag = nullptr; size_t tm_flag_bytes = 0;   // [T][nbook] gprune safe: (frame, codebook)s whose list depends on the visiting order
   char last_kernel[64] = {0};
   // pinned staging copy of the running call's utterance boundaries (history pruning only) and the event behind its
   // upload: the buffer is rewritten only when the copy that read it is done
@@ -60,7 +61,7 @@ JAMD_GMM_LOCAL int jamd_gmm_launch_dens(jamd_gmm *g, const float *rec, int E, co
 // ---- gmm_pruned.hip
 // Plain states under gprune safe (K1s).
 int jamd_gmm_launch_safe(jamd_gmm *g, const float *frames, int T, float *out, hipStream_t st);
-// Tied-mixture states: the codebook cache c_score / c_id / c_num (K2, or K2h with history pruning: needs the call's
-// utterance boundaries in d_cur_utt_off), then -- unless out is NULL -- the states' scores from it.
+// Tied-mixture states: the codebook cache c_score / c_id / c_num (K2, or K2h with history pruning; under any pruning
+// the call's utterance boundaries are needed in d_cur_utt_off), then -- unless out is NULL -- the states' scores from it.
 int jamd_gmm_launch_tmix(jamd_gmm *g, const float *frames, int T, float *out, float *c_score,
                          int *c_id, int *c_num, hipStream_t st);

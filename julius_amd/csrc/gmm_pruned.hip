@@ -10,10 +10,14 @@
 // its partial sum already exceeds the running N-th best, so the surviving list
 // is the N highest compute_g_base() scores in descending order.  The device
 // therefore evaluates every Gaussian fully (same 4-op chain as K1) and keeps a
-// register-resident sorted top-N per frame with cache_push()'s insertion rule.
-// (With exactly tied scores the reference's survivor depends on its visiting
-// order, which for tied-mixture frames t>0 starts from frame t-1's winners;
-// the device visits in index order.  See DESIGN.md "ties".)
+// register-resident sorted top-N per frame with cache_push()'s insertion rule;
+// where the N-th best score lies below LOG_ZERO itself the reference's list is
+// no longer that, see topn_push_safe().
+// With exactly tied scores, and on such far frames, the reference's list depends
+// on its visiting order, which for tied-mixture frames t>0 starts from frame
+// t-1's winners.  The frame-parallel codebook kernel visits in index order and
+// marks the (frame, codebook)s where the order can show; those are done again
+// in the reference's order by tmix_book_safe_order_kernel.
 //
 // Same lane = frame-pair mapping as the tile kernel: Gaussian records come
 // through scalar loads, the D-loop is packed VALU.
@@ -54,8 +58,8 @@ gmm_safe_kernel(const float *__restrict__ rec, const int *__restrict__ st_off,
     for (int i = 0; i < NMAX; i++) { sc0[i] = sc1[i] = JAMD_LOG_ZERO; id0[i] = id1[i] = 0; }
     for (int e = e0; e < e1; e++) {
       const f2 g = gauss_pair<DT>(v, vt, lane, D, rec + (size_t)e * REC);
-      topn_push<NMAX>(sc0, id0, len0, cap, g.x, e - e0);
-      topn_push<NMAX>(sc1, id1, len1, cap, g.y, e - e0);
+      topn_push_safe<NMAX>(sc0, id0, len0, cap, g.x, e - e0);
+      topn_push_safe<NMAX>(sc1, id1, len1, cap, g.y, e - e0);
     }
     // calc_mix.c:66-72: add ln w of the survivors, log-sum from the last slot down
     float y0 = JAMD_LOG_ZERO, y1 = JAMD_LOG_ZERO;
@@ -88,8 +92,8 @@ template <int DT, int NMAX>
 __global__ void __launch_bounds__(64 * kWaves)
 tmix_book_kernel(const float *__restrict__ brec, const int *__restrict__ book_off,
                  const float *__restrict__ frames, float *__restrict__ c_score,
-                 int *__restrict__ c_id, int *__restrict__ c_num, int T, int nbook, int D, int REC,
-                 int cap) {
+                 int *__restrict__ c_id, int *__restrict__ c_num, int *__restrict__ c_flag, int T, int nbook, int D,
+                 int REC, int cap) {
   extern __shared__ __align__(16) float dyn[];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int t0 = (blockIdx.x * kWaves + wave) * 128;
@@ -116,11 +120,16 @@ tmix_book_kernel(const float *__restrict__ brec, const int *__restrict__ book_of
     int len0 = 0, len1 = 0;
 #pragma unroll
     for (int i = 0; i < N; i++) { sc0[i] = sc1[i] = JAMD_LOG_ZERO; id0[i] = id1[i] = 0; }
+    bool ord0 = false, ord1 = false;
     for (int k = k0; k < k1; k++) {
       const f2 g = gauss_pair<DT>(v, vt, lane, D, brec + (size_t)k * REC);
-      topn_push<N>(sc0, id0, len0, cap, g.x, k - k0);
-      topn_push<N>(sc1, id1, len1, cap, g.y, k - k0);
+      ord0 |= topn_order_shows<N>(sc0, len0, g.x);
+      ord1 |= topn_order_shows<N>(sc1, len1, g.y);
+      topn_push_safe<N>(sc0, id0, len0, cap, g.x, k - k0);
+      topn_push_safe<N>(sc1, id1, len1, cap, g.y, k - k0);
     }
+    if (ta < T) c_flag[(size_t)ta * nbook + b] = ord0;
+    if (tb < T) c_flag[(size_t)tb * nbook + b] = ord1;
 #pragma unroll
     for (int i = 0; i < N; i++) {
       if (i < cap) {
@@ -165,6 +174,11 @@ struct TopList {                 // lane p holds entry p of the descending list 
     if (lane == p) { sc = score; id = gid; }
     if (len < cap) len++;
   }
+  // the branch without history: compute_g_safe()'s LOG_ZERO for a Gaussian below a full list's last entry (topn_push_safe(), gmm_dev.h)
+  __device__ __forceinline__ void push_safe(float score, int gid, int lane) {
+    if (len == cap && score < __shfl(sc, cap - 1, 64)) score = JAMD_LOG_ZERO;
+    push(score, gid, lane);
+  }
 };
 
 template <int METHOD>
@@ -205,7 +219,7 @@ tmix_book_hist_kernel(const float *__restrict__ brec, const int *__restrict__ bo
         while (m) {
           const int l = __ffsll((long long)m) - 1;
           m &= m - 1ull;
-          L.push(__shfl(sc, l, 64), i0 + l, lane);
+          L.push_safe(__shfl(sc, l, 64), i0 + l, lane);
         }
       }
     } else {
@@ -289,6 +303,83 @@ tmix_book_hist_kernel(const float *__restrict__ brec, const int *__restrict__ bo
   }
 }
 
+// ---- tied-mixture codebooks, gprune safe: the frames where the visiting order shows -------------------------
+// gprune_safe() called from calc_tied_mix() with last_id = the codebook's winners of frame t - 1 (gprune_safe.c:166-183):
+// those are scored by compute_g_base() and pushed first, then every other Gaussian in index order by compute_g_safe()
+// against the list's last score, dropped unless above it.  tmix_book_kernel has visited in index order; where that can
+// give another list (c_flag: an exactly tied score, or a score at or below LOG_ZERO) this kernel does the frame again in
+// the reference's order, one wave per (codebook, utterance) walking the marked frames in order -- a marked frame's
+// predecessor may be one it has just rewritten.  An utterance's first frame has no history: index order is its order.
+__global__ void __launch_bounds__(64)
+tmix_book_safe_order_kernel(const float *__restrict__ brec, const int *__restrict__ book_off, const float *__restrict__ frames,
+                            const int *__restrict__ utt_off, const int *__restrict__ c_flag, float *__restrict__ c_score,
+                            int *__restrict__ c_id, int *__restrict__ c_num, int nutt, int nbook, int D, int REC, int cap) {
+  extern __shared__ __align__(16) float dyn[];
+  float *x = dyn;                                      // [D]    the frame
+  int *calced = reinterpret_cast<int *>(x + D);        // [K]    mixcalced
+  const int lane = threadIdx.x, b = blockIdx.x;
+  const int k0 = book_off[b], K = book_off[b + 1] - k0;
+  for (int i = lane; i < K; i += 64) calced[i] = 0;
+  TopList L; L.sc = JAMD_LOG_ZERO; L.id = 0; L.len = 0; L.cap = cap;
+  int kept_t = -1;                                     // the frame whose list the registers hold
+  wave_sync();
+  for (int u = blockIdx.y; u < nutt; u += gridDim.y)   // gridDim.y is capped (65535 limit): utterances are strided
+  for (int c0 = utt_off[u] + 1, t_end = utt_off[u + 1]; c0 < t_end; c0 += 64) {
+    const int tc = c0 + lane;
+    unsigned long long marked = __ballot(tc < t_end && c_flag[(size_t)tc * nbook + b] != 0);
+    while (marked) {
+      const int t = c0 + __ffsll((long long)marked) - 1;
+      marked &= marked - 1ull;
+      int last_id, lnum;
+      if (kept_t == t - 1) { last_id = L.id; lnum = L.len; }
+      else {
+        lnum = c_num[(size_t)(t - 1) * nbook + b];
+        last_id = lane < lnum ? c_id[((size_t)(t - 1) * nbook + b) * cap + lane] : 0;
+      }
+      if (lnum == 0) continue;                         // nothing cached for frame t - 1: no history
+      for (int d = lane; d < D; d += 64) x[d] = frames[(size_t)t * D + d];
+      wave_sync();
+      auto g_base = [&](int i) {                       // compute_g_base(), the operation order of gauss_pair()
+        const float *__restrict__ r = brec + (size_t)(k0 + i) * REC;
+        const float gc = r[2 * D];
+        float acc = gc;
+        for (int d = 0; d < D; d++) { float v = x[d] - r[d]; v = v * v; v = v * r[D + d]; acc = acc + v; }
+        return (gc != gc) ? JAMD_LOG_ZERO : acc * -0.5f;
+      };
+      float psc = JAMD_LOG_ZERO;
+      if (lane < lnum) { psc = g_base(last_id); calced[last_id] = 1; }
+      wave_sync();
+      L.len = 0;
+      for (int j = 0; j < lnum; j++) L.push(__shfl(psc, j, 64), __shfl(last_id, j, 64), lane);
+      float thres = __shfl(L.sc, L.len - 1, 64);
+      for (int i0 = 0; i0 < K; i0 += 64) {
+        const int i = i0 + lane;
+        float sc = JAMD_LOG_ZERO;
+        bool cand = false;
+        if (i < K) {
+          if (calced[i]) calced[i] = 0;
+          else { sc = g_base(i); cand = true; }
+        }
+        unsigned long long m = __ballot(cand);
+        while (m) {
+          const int l = __ffsll((long long)m) - 1;
+          m &= m - 1ull;
+          float s_l = __shfl(sc, l, 64);
+          if (s_l < thres) s_l = JAMD_LOG_ZERO;        // compute_g_safe(): the partial sum passed -2 x thres
+          if (s_l <= thres) continue;
+          L.push(s_l, i0 + l, lane);
+          thres = __shfl(L.sc, L.len - 1, 64);
+        }
+      }
+      const size_t o = ((size_t)t * nbook + b) * cap;
+      if (lane < L.len) { c_score[o + lane] = L.sc; c_id[o + lane] = L.id; }
+      if (lane == 0) c_num[(size_t)t * nbook + b] = L.len;
+      kept_t = t;
+      wave_sync();
+    }
+  }
+}
+
 // ---- tied-mixture states: weights of the cached winners + log-sum -----------
 __global__ void __launch_bounds__(256)
 tmix_state_kernel(const int *__restrict__ tied_states, int ntied, const int *__restrict__ st_off,
@@ -363,11 +454,20 @@ int launch_book(jamd_gmm *g, const float *frames, int T, float *c_score, int *c_
     const int rc = jamd_reserve_dyn_lds((const void *)tmix_book_kernel<DT, N>, dyn, "tied-mixture codebooks");
     if (rc != JAMD_OK) return rc;
     hipLaunchKernelGGL((tmix_book_kernel<DT, N>), grid, dim3(64 * kWaves), dyn, st, g->d_book_rec,
-                       g->d_book_off, frames, c_score, c_id, c_num, T, g->nbook, g->D, g->rec, cap);
+                       g->d_book_off, frames, c_score, c_id, c_num, g->d_tm_flag, T, g->nbook, g->D, g->rec, cap);
     return JAMD_OK;
   };
   if (g->gprune == JAMD_GPRUNE_NONE) return launch(std::integral_constant<int, 0>{});
-  return dispatch_topn<2>(cap, launch);
+  int rc = jamd_grow(&g->d_tm_flag, &g->tm_flag_bytes, sizeof(int) * (size_t)T * g->nbook);
+  if (rc != JAMD_OK) return rc;
+  if ((rc = dispatch_topn<2>(cap, launch)) != JAMD_OK) return rc;
+  // ... and the marked frames again in the reference's visiting order
+  const size_t odyn = sizeof(float) * (size_t)g->D + sizeof(int) * (size_t)g->maxbook;
+  if ((rc = jamd_reserve_dyn_lds((const void *)tmix_book_safe_order_kernel, odyn, "gprune safe over tied-mixture codebooks")) != JAMD_OK) return rc;
+  hipLaunchKernelGGL(tmix_book_safe_order_kernel, dim3(g->nbook, g->cur_nutt < 65535 ? g->cur_nutt : 65535), dim3(64), odyn, st,
+                     g->d_book_rec, g->d_book_off, frames, g->d_cur_utt_off, g->d_tm_flag, c_score, c_id, c_num, g->cur_nutt,
+                     g->nbook, g->D, g->rec, cap);
+  return JAMD_OK;
 }
 
 }  // namespace

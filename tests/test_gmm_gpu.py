@@ -343,3 +343,53 @@ def test_cdset_vs_oracle_with_log_zero_members(engine, oracle):
         got = lib.CdSet(engine, set_off, states, code, nb).outprob_host(scores)
         want = oracle.outprob_cd(scores, set_off, states, code, nb)
         assert np.array_equal(got, want, equal_nan=True), (code, nb)
+
+
+def _cd_case(nset, T, seed):
+    """Scores [T][200] and state sets for the cdset kernel's edges.  Columns 0-19 are live on every frame, columns 10-19
+    copies of 0-9 (equal scores), columns 20-21 LOG_ZERO on every frame, a fifth of the rest LOG_ZERO.  Sets: empty,
+    one member, empty, 17 live members (eight states twice and a ninth, so the 15th and 16th best are equal and so
+    are the first two), 40 members, all-LOG_ZERO, then random sets of 0-12 members; members may repeat a state."""
+    rng = np.random.default_rng(seed)
+    S = 200
+    scores = rng.normal(-40, 10, size=(T, S)).astype(np.float32)
+    scores[:, 22:][rng.random((T, S - 22)) < 0.2] = -1000000.0
+    scores[:, 10:20] = scores[:, 0:10]
+    scores[:, 20:22] = -1000000.0
+    sets = [[], [int(rng.integers(0, 20))], [], list(range(8)) + list(range(10, 18)) + [8],
+            list(rng.integers(0, S, size=40)), [20, 21]]
+    sets += [list(rng.integers(0, S, size=int(k))) for k in rng.integers(0, 13, size=nset - len(sets))]
+    set_off = np.concatenate([[0], np.cumsum([len(x) for x in sets])]).astype(np.int32)
+    states = np.array([s for x in sets for s in x], np.int32)
+    assert len(sets) == nset and [len(x) for x in sets[:6]] == [0, 1, 0, 17, 40, 2]
+    return scores, set_off, states
+
+
+CD_METHODS = [(lib.IWCD_MAX, 3), (lib.IWCD_AVG, 3), (lib.IWCD_NBEST, 1), (lib.IWCD_NBEST, 15), (lib.IWCD_NBEST, 16)]
+
+
+@pytest.mark.parametrize("nset", [255, 256, 257, 600])
+def test_cdset_empty_sets_repeated_members_and_a_second_block(engine, oracle, nset):
+    """State sets around the kernel's 256-thread block and beyond it; empty and all-LOG_ZERO sets (avg and nbest give
+    0/0 = NaN as the reference's float division does, max gives LOG_ZERO); nbest at its largest list (16) with 17 live
+    members, and equal scores on both sides of where the list ends."""
+    scores, set_off, states = _cd_case(nset, 9, nset)
+    for code, nb in CD_METHODS:
+        got = lib.CdSet(engine, set_off, states, code, nb).outprob_host(scores)
+        want = oracle.outprob_cd(scores, set_off, states, code, nb)
+        assert np.isnan(want[:, [0, 2, 5]]).all() == (code != lib.IWCD_MAX) and np.isfinite(want[:, [1, 3, 4]]).all()
+        assert np.array_equal(got, want, equal_nan=True), (code, nb)
+
+
+@pytest.mark.parametrize("code,nb", [(lib.IWCD_AVG, 3), (lib.IWCD_NBEST, 16), (lib.IWCD_NBEST, 3)])
+def test_cdset_more_frames_than_the_grid_has_rows(engine, oracle, code, nb):
+    """Beyond 4096 frames the kernel strides over the frames: avg and nbest (the long tied-mixture call above sees max)."""
+    scores, set_off, states = _cd_case(8, 4100, 3)
+    got = lib.CdSet(engine, set_off, states, code, nb).outprob_host(scores)
+    assert np.array_equal(got, oracle.outprob_cd(scores, set_off, states, code, nb), equal_nan=True)
+
+
+@pytest.mark.parametrize("nb", [0, 17])
+def test_cdset_nbest_outside_the_list_is_refused(engine, nb):
+    with pytest.raises(lib.JamdError):
+        lib.CdSet(engine, np.array([0, 2], np.int32), np.array([0, 1], np.int32), lib.IWCD_NBEST, nb)

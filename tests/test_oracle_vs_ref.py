@@ -4,6 +4,7 @@ the dev container builds from /root/reference (oracle/Makefile)."""
 import numpy as np
 import pytest
 
+import tiedref
 from densref import dens_ref, gmax_winners, visiting_order_covered
 from julius_amd import synth
 from oracle import pyoracle as po
@@ -181,3 +182,104 @@ def test_verification_gmm(oracle, ref, tmp_path, num, null_frac):
         sums, winner, cm, valid, nframe = eng.gmm_result()
         assert nframe == len(fr) and valid
         assert np.array_equal(oracle.rejgmm_accumulate(got), sums) and int(np.argmax(sums)) == winner
+
+
+# ------------------------------------------------- shapes of tests/test_gmm_pruned_edges_gpu.py: the oracle's licence
+CODES = {"safe": po.GPRUNE_SAFE, "heu": po.GPRUNE_HEU, "beam": po.GPRUNE_BEAM}
+
+
+@pytest.mark.parametrize("sizes", [(3, 70, 64, 1, 129), (65, 8)])
+@pytest.mark.parametrize("dup", [False, True])
+def test_tied_gmm_unequal_codebooks(ref, oracle, tmp_path, sizes, dup):
+    """Codebooks of unequal size (one of a single Gaussian, one smaller than the list) under safe / heu / beam at list
+    sizes below, between and above the codebook sizes, with and without exactly tied Gaussians: state scores and the
+    MIXCACHE of every codebook, oracle == compiled reference."""
+    m = tiedref.make_tied(sizes, S=21, D=39, seed=len(sizes) + dup, dup=dup)
+    fr = synth.make_frames(m, T=30, seed=11, noise=2.0)
+    for gprune in ("safe", "heu", "beam"):
+        for n in (1, 4, 17, 64):
+            am, ex = tiedref.load_tied(ref, tmp_path, m, gprune, n)
+            assert np.array_equal(oracle.gmm_outprob(ex, fr, CODES[gprune], n), am.outprob(fr)), (gprune, n)
+            for b in range(len(sizes)):
+                sc, ids, num = am.tmix_cache(fr, b, n)
+                osc, oids, onum = oracle.tmix_topn(ex, b, fr, CODES[gprune], n)
+                assert np.array_equal(num, onum), (gprune, n, b)
+                for t in range(len(fr)):
+                    k = num[t]
+                    assert np.array_equal(ids[t, :k], oids[t, :k]) and np.array_equal(sc[t, :k], osc[t, :k]), (gprune, n, b, t)
+            am.close()
+
+
+@pytest.mark.parametrize("n", [1, 2, 3, 4, 5])
+def test_plain_safe_with_triplicated_densities(ref, oracle, n):
+    """Exact score ties inside plain states under safe pruning: entries 1 and 3 share entry 0's density."""
+    m = tiedref.triplicate(synth.make_gmm(S=20, M=6, D=39, seed=31, ragged=True, null_frac=0.05))
+    fr = synth.make_frames(m, T=40, seed=32)
+    want = ref.am_from_flat(m, gprune="safe", gprune_num=n).outprob(fr)
+    assert np.array_equal(oracle.gmm_outprob(m, fr, po.GPRUNE_SAFE, n), want)
+    assert np.array_equal(oracle.gmm_outprob(m, tiedref.far_frames(fr), po.GPRUNE_SAFE, n),
+                          ref.am_from_flat(m, gprune="safe", gprune_num=n).outprob(tiedref.far_frames(fr)))
+
+
+@pytest.mark.parametrize("num", [8, 32])
+def test_verification_gmm_with_identical_mixtures(oracle, ref, tmp_path, num):
+    """-gmmnum 8 and 32 (list sizes of their own on the device) with a model file in which two mixtures of one GMM
+    are the same Gaussian: gmm.c's private pruning under exact ties, through the reference's own entry points."""
+    task = synth.make_triphone_task(tmp_path, seed=12, nword=60)
+    gpath, model, names = synth.make_rejection_gmm(tmp_path, task["model"]["centre"], seed=40 + num, M=40, ragged=False)
+    for s in range(len(names)):
+        e0 = int(model["st_off"][s])
+        for k in (2, 39):
+            model["mean"][model["ent_dens"][e0 + k]] = model["mean"][model["ent_dens"][e0]]
+            model["var"][model["ent_dens"][e0 + k]] = model["var"][model["ent_dens"][e0]]
+    tiedref.write_rejection_gmm(gpath, model, names)
+    eng = po.RefEngine(ref, ["-h", task["hmmdefs"], "-hlist", task["hmmlist"], "-v", task["dict"], "-nlr", task["arpa"],
+                             "-input", "htkparam", "-gprune", "none", "-b", "120", "-gmm", str(gpath), "-gmmnum", str(num)])
+    info = eng.gmm_info()
+    assert info["nmodel"] == len(names) and info["gprune_num"] == num
+    g = info["model"]
+    e0 = int(g["st_off"][info["model_state"][0]])
+    d0, d2 = g["ent_dens"][e0], g["ent_dens"][e0 + 2]
+    assert np.array_equal(g["mean"][d0], g["mean"][d2]) and np.array_equal(g["ivar"][d0], g["ivar"][d2])
+    fr, _ = synth.make_utterance(task, nwords=3, seed=71)
+    assert np.array_equal(oracle.rejgmm_frame_scores(info, fr), eng.gmm_frame_scores(fr))
+
+
+@pytest.mark.parametrize("sizes,n", [((16, 16), 2), ((16, 16), 16), ((65, 8), 2), ((65, 8), 4)])
+def test_tied_safe_visiting_order_shows_under_exact_ties(oracle, sizes, n):
+    """The premise of the GPU suite's tie case: with duplicated Gaussians in a codebook, tied-mixture safe pruning
+    that starts from frame t - 1's winners (the reference, and the oracle over a whole utterance) gives other state
+    scores than the same frames visited in index order (the oracle frame by frame)."""
+    m = tiedref.make_tied(sizes, S=21, D=39, seed=7, dup=True)
+    fr = synth.make_frames(m, T=75, seed=8, noise=2.0)
+    full = oracle.gmm_outprob(m, fr, po.GPRUNE_SAFE, n)
+    single = tiedref.frame_by_frame(oracle, m, fr, po.GPRUNE_SAFE, n)
+    assert np.array_equal(full[0], single[0])
+    rows = int((full != single).any(axis=1).sum())
+    print(f"tie case {sizes} N={n}: {rows} of {len(fr)} rows differ")
+    assert rows >= 1
+
+
+@pytest.mark.parametrize("gprune", ["safe", "heu", "beam"])
+@pytest.mark.parametrize("n", [3, 16])
+def test_tied_gmm_far_frames(ref, oracle, tmp_path, gprune, n):
+    """Frames 50 and 400 times too far out, the first frame of the utterance among them: where the kept scores lie below
+    LOG_ZERO, compute_g_safe()'s LOG_ZERO for a pruned Gaussian is above the list's last entry and enters the list."""
+    m = tiedref.make_tied((16, 24), S=21, D=39, seed=32)
+    fr = tiedref.far_frames(synth.make_frames(m, T=40, seed=33, noise=2.0))
+    fr[0] *= np.float32(400.0)
+    am, ex = tiedref.load_tied(ref, tmp_path, m, gprune, n)
+    want = am.outprob(fr)
+    assert np.array_equal(oracle.gmm_outprob(ex, fr, CODES[gprune], n), want)
+    assert (want == np.float32(-1000000.0)).any()
+    lz = 0
+    for b in range(2):
+        sc, ids, num = am.tmix_cache(fr, b, n)
+        osc, oids, onum = oracle.tmix_topn(ex, b, fr, CODES[gprune], n)
+        assert np.array_equal(num, onum)
+        for t in range(len(fr)):
+            k = num[t]
+            assert np.array_equal(ids[t, :k], oids[t, :k]) and np.array_equal(sc[t, :k], osc[t, :k]), (b, t)
+            lz += int((sc[t, :k] == np.float32(-1000000.0)).sum())
+    assert lz > 0
+    am.close()
