@@ -658,9 +658,14 @@ int  jamd_beam_trellis(jamd_beam *b, int utt, jamd_trellis_atom *atoms, int cap,
  * paramtype is an HTK parameter kind code: base JAMD_F_MFCC / _FBANK / _MELSPEC ORed with the
  * qualifier bits below (htk_defs.h:57-66); vecsize the vector size the acoustic model declares.
  *
+ * Spectral subtraction (-sscalc [-sscalclen], -ssload, -ssalpha, -ssfloor) is served through
+ * jamd_frontend_set_ss() on the created object, bit-identical as well (MakeFBank(), mfcc-core.c:473-487;
+ * new_SS_calculate(), ss.c:110-172).
+ *
  * NOT SERVED -- jamd_frontend_create() returns JAMD_EINVAL and says why (there is no host front end
  * behind this library):
- *   - spectral subtraction (-sscalc, -ssload): ss != 0;
+ *   - ss != 0 in the descriptor: the descriptor carries none of the parameters of spectral subtraction,
+ *     which is switched on with jamd_frontend_set_ss();
  *   - realtime input and MAP-CMN (the pipelined front end of wav2mfcc-pipe.c): realtime != 0;
  *   - kinds other than MFCC, FBANK and MELSPEC, FBANK / MELSPEC with _E or _0 (WMP_calc() leaves
  *     those slots unwritten), _N without _E and _D, _A without _D. */
@@ -692,7 +697,7 @@ typedef struct {
   const float *cvar_init;
   int static_cvn_only;
   int splice;                         /* -splice N (1 = none)                                             */
-  int ss, realtime;                   /* refused: spectral subtraction / realtime or MAP-CMN             */
+  int ss, realtime;                   /* refused: see NOT SERVED (SS: jamd_frontend_set_ss()) / realtime  */
 } jamd_frontend_desc;
 
 typedef struct jamd_frontend jamd_frontend;
@@ -727,6 +732,40 @@ int  jamd_frontend_run_dev(jamd_frontend *f, const int16_t *dev_samples, const i
                            float *dev_out, int *frame_off, void *stream);
 int  jamd_frontend_run_host(jamd_frontend *f, const int16_t *samples, const int64_t *sample_off, int nutt,
                             float *out, int *frame_off);
+
+/* Spectral subtraction.  jamd_frontend_set_ss() switches it on a created object; it may be called between runs
+ * (the rule of one stream per object covers it), and every later jamd_frontend_run_*() applies it:
+ *   JAMD_SS_CALC  the noise spectrum of every utterance is new_SS_calculate() over its first
+ *                 min(calc_len_ms * smp_freq / 1000, length) samples, computed on the same stream before the
+ *                 frames, into the object's scratch (8 * fftN bytes per head frame).  calc_len_ms * smp_freq / 1000
+ *                 < framesize is refused (the reference's start-up rule, m_fusion.c:1403-1412);
+ *   JAMD_SS_LOAD  one spectrum (host array of fftN floats, uploaded once by the call) for every utterance;
+ *                 noise == NULL or noise_len != fftN is refused;
+ *   JAMD_SS_OFF   the front end without spectral subtraction.
+ * A refused call (also an unknown mode) leaves the object as it was.  Where the reference divides 0 by 0 (|X| == 0
+ * over a noise entry of 0, or alpha 0) the features are NaN here too. */
+#define JAMD_SS_OFF  0
+#define JAMD_SS_CALC 1            /* -sscalc [-sscalclen]: noise spectrum from the head of every utterance */
+#define JAMD_SS_LOAD 2            /* -ssload: one spectrum for every utterance */
+typedef struct {
+  int mode, calc_len_ms;          /* -sscalclen */
+  float alpha, floor;             /* -ssalpha, -ssfloor */
+  const float *noise; int noise_len;   /* JAMD_SS_LOAD: host array, must be fftN long */
+} jamd_frontend_ss;
+int  jamd_frontend_ss_default(jamd_frontend_ss *ss);                 /* OFF, 300, DEF_SSALPHA, DEF_SSFLOOR, NULL, 0 */
+int  jamd_frontend_set_ss(jamd_frontend *f, const jamd_frontend_ss *ss);
+int  jamd_frontend_fftn(const jamd_frontend *f);
+/* new_SS_calculate() per utterance over its first min(head_samples, length) samples (head_samples <= 0: the whole
+ * utterance, which is what mkss computes): out [nutt][fftN] float.  An utterance whose head holds no full frame:
+ * JAMD_EINVAL, nothing written.  Uses the object's scratch like jamd_frontend_run_dev(). */
+int  jamd_frontend_noise_dev (jamd_frontend *f, const int16_t *dev_samples, const int64_t *sample_off, int nutt,
+                              int64_t head_samples, float *dev_noise, void *stream);
+int  jamd_frontend_noise_host(jamd_frontend *f, const int16_t *samples, const int64_t *sample_off, int nutt,
+                              int64_t head_samples, float *noise);
+/* host only: the mkss / -ssload file format (big-endian int32 count, then that many big-endian float32).  read
+ * returns the count in the file (copies min(count, cap)); a file shorter than its count is refused. */
+int  jamd_frontend_ss_read (const char *path, float *out, int cap);
+int  jamd_frontend_ss_write(const char *path, const float *noise, int n);
 
 #ifdef __cplusplus
 }

@@ -10,12 +10,16 @@
 // independent is spread over lanes: samples, pre-emphasis, the window, the butterflies of an FFT
 // stage, the bins, the coefficients, the frames.
 //
-//   fe_frame_kernel   one wave per frame, four frames per workgroup: WMP_calc() -> statics[T][baselen]
+//   fe_frame_kernel   one wave per frame, four frames per workgroup: WMP_calc() -> statics[T][baselen]; its
+//                     instantiation <true> carries the spectral subtraction of MakeFBank() behind the FFT
+//   fe_noise_frame    one wave per head frame: |X| of all fftN indices in double (new_SS_calculate(), ss.c:110-172)
+//   fe_noise_mean     one lane per (utterance, FFT index): the float chain over the head frames, then / framenum
 //   fe_emax_kernel    one workgroup per utterance: the max of NormaliseLogE() (order-free)
 //   fe_feat_kernel    one lane per (frame, element): normalised energy, Delta(), Accel() -> feat[T][veclen]
 //   fe_stats_kernel   one lane per (utterance, dimension): the serial float sums of CMN() / MVN()
 //   fe_write_kernel   one lane per output element: normalisation and splicing -> out[T'][veclen * splice]
 #include "jamd_device.h"
+#include "ss_file.h"
 #include <cmath>
 #include <cstdint>
 
@@ -185,26 +189,13 @@ __device__ __forceinline__ int fe_find(const int *off, int n, int g) {   // u wi
   return lo;
 }
 
-// LDS per wave: Re[fftN] | Im[fftN] | A[nv2 + 1] (double; also the bit-reversal staging) | fb[fbank_num + 1] | misc[2]
-__global__ void __launch_bounds__(64 * kFeFrames)
-fe_frame_kernel(FeParams p, const int16_t *__restrict__ samples, const long long *__restrict__ soff,
-                const int *__restrict__ foff, int Ttot, float *__restrict__ statics) {
-  extern __shared__ double fe_lds[];
-  const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
+// One window -> its spectrum in xr / xi: load, ZMeanFrame(), PreEmphasise(), Hamming(), zero padding, FFT().  This
+// is the first half of WMP_calc() and the whole per-frame work of new_SS_calculate(); the two energy sums of
+// WMP_calc() sit at their places in it (kEnergy; new_SS_calculate() has no energy term).  Returns the log energy
+// on lane 0.  (FeParams by value: by reference the register allocation of the whole frame kernel changes.)
+template <bool kEnergy>
+__device__ __forceinline__ float fe_spectrum(const FeParams p, const int16_t *wave, int lane, float *xr, float *xi, float *tmp, double *misc) {
   const int nv2 = p.fftN >> 1;
-  const size_t per = (size_t)p.fftN + (nv2 + 1) + (p.fbank_num + 1) + 2;   // doubles per wave
-  double *base = fe_lds + per * wv;
-  float *xr = (float *)base, *xi = xr + p.fftN;
-  double *A = base + p.fftN, *fb = A + nv2 + 1, *misc = fb + p.fbank_num + 1;
-  float *tmp = (float *)A;
-
-  const int g = blockIdx.x * (int)(blockDim.x >> 6) + wv;   // kFeFrames waves per workgroup, fewer for fftN 4096
-  const bool valid = g < Ttot;
-  const int gg = valid ? g : Ttot - 1;       // idle waves recompute the last frame (same barriers), store nothing
-  const int u = fe_find(foff, p.nutt, gg);
-  const long long s0 = soff[u] + (long long)(gg - foff[u]) * p.frameshift;
-  const int16_t *wave = samples + s0;
-
   for (int i = lane; i < p.fftN; i += 64) { xr[i] = i < p.framesize ? (float)wave[i] : 0.0f; xi[i] = 0.0f; }
   __syncthreads();
   if (p.zmean) {                              // ZMeanFrame(): float sum in sample order
@@ -220,7 +211,7 @@ fe_frame_kernel(FeParams p, const int16_t *__restrict__ samples, const long long
     __syncthreads();
   }
   float energy = 0.0f;
-  if (p.energy && p.raw_e && lane == 0) {     // CalcLogRawE(): double accumulator of float products
+  if (kEnergy && p.energy && p.raw_e && lane == 0) {     // CalcLogRawE(): double accumulator of float products
     double raw_E = 0.0;
     for (int i = 0; i < p.framesize; i++) raw_E += xr[i] * xr[i];
     energy = (float)log(raw_E);
@@ -234,7 +225,7 @@ fe_frame_kernel(FeParams p, const int16_t *__restrict__ samples, const long long
     xi[i] = 0.0f;
   }
   __syncthreads();
-  if (p.energy && !p.raw_e && lane == 0) {
+  if (kEnergy && p.energy && !p.raw_e && lane == 0) {
     double raw_E = 0.0;
     for (int i = 0; i < p.framesize; i++) raw_E += xr[i] * xr[i];
     energy = (float)log(raw_E);
@@ -257,6 +248,50 @@ fe_frame_kernel(FeParams p, const int16_t *__restrict__ samples, const long long
       xr[i] = (float)(ar + tRe);  xi[i] = (float)(ai + tIm);
     }
     __syncthreads();
+  }
+  return energy;
+}
+
+// LDS per wave: Re[fftN] | Im[fftN] | A[nv2 + 1] (double; also the bit-reversal staging) | fb[fbank_num + 1] | misc[2]
+// noise / nstride / alpha / floor_ are read by the <true> instantiation only: the spectrum of utterance u is
+// noise + u * nstride (-sscalc: nstride fftN; -ssload: one spectrum for all, nstride 0).
+template <bool kSS>
+__global__ void __launch_bounds__(64 * kFeFrames)
+fe_frame_kernel(FeParams p, const int16_t *__restrict__ samples, const long long *__restrict__ soff,
+                const int *__restrict__ foff, int Ttot, float *__restrict__ statics, const float *__restrict__ noise,
+                int nstride, float alpha, float floor_) {
+  extern __shared__ double fe_lds[];
+  const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int nv2 = p.fftN >> 1;
+  const size_t per = (size_t)p.fftN + (nv2 + 1) + (p.fbank_num + 1) + 2;   // doubles per wave
+  double *base = fe_lds + per * wv;
+  float *xr = (float *)base, *xi = xr + p.fftN;
+  double *A = base + p.fftN, *fb = A + nv2 + 1, *misc = fb + p.fbank_num + 1;
+  float *tmp = (float *)A;
+
+  const int g = blockIdx.x * (int)(blockDim.x >> 6) + wv;   // kFeFrames waves per workgroup, fewer for fftN 4096
+  const bool valid = g < Ttot;
+  const int gg = valid ? g : Ttot - 1;       // idle waves recompute the last frame (same barriers), store nothing
+  const int u = fe_find(foff, p.nutt, gg);
+  const long long s0 = soff[u] + (long long)(gg - foff[u]) * p.frameshift;
+  const int16_t *wave = samples + s0;
+  const float energy = fe_spectrum<true>(p, wave, lane, xr, xi, tmp, misc);
+  if (kSS) {
+    // MakeFBank()'s spectral subtraction (mfcc-core.c:473-487) over the indices the filter bank reads; every lane
+    // rewrites the k it reads below, so the barrier behind the FFT is all this needs.  P == 0 over a zero noise
+    // entry divides 0 by 0: NaN, as there.
+    const float *np = noise + (size_t)u * nstride;
+    for (int k = p.klo + lane; k <= p.khi; k += 64) {
+      const double Re = xr[k - 1], Im = xi[k - 1];
+      const double P = sqrt(Re * Re + Im * Im);
+      const double NP = np[k - 1];
+      const double d = P * P - alpha * NP * NP;
+      double H;
+      if (d < 0) H = floor_;
+      else H = sqrt(d) / P;
+      xr[k - 1] = (float)(H * Re);
+      xi[k - 1] = (float)(H * Im);
+    }
   }
   // MakeFBank(): |X| (or |X|^2) per FFT index, then every bin sums its k in ascending order
   for (int k = p.klo + lane; k <= p.khi; k += 64) {
@@ -302,6 +337,52 @@ fe_frame_kernel(FeParams p, const int16_t *__restrict__ samples, const long long
     }
     if (p.energy) out[q] = energy;
   }
+}
+
+// new_SS_calculate() (ss.c:130-161), the part per frame: |X| of every FFT index of head frame g, in double, to
+// mag[g][fftN].  `hoff` holds the head frames of the utterances back to back, as foff holds all their frames; the grid
+// decode and the LDS carve are the frame kernel's.
+__global__ void __launch_bounds__(64 * kFeFrames)
+fe_noise_frame(FeParams p, const int16_t *__restrict__ samples, const long long *__restrict__ soff,
+               const int *__restrict__ hoff, int Htot, double *__restrict__ mag) {
+  extern __shared__ double fe_lds[];
+  const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int nv2 = p.fftN >> 1;
+  const size_t per = (size_t)p.fftN + (nv2 + 1) + (p.fbank_num + 1) + 2;   // doubles per wave
+  double *base = fe_lds + per * wv;
+  float *xr = (float *)base, *xi = xr + p.fftN;
+  double *A = base + p.fftN, *misc = A + (nv2 + 1) + (p.fbank_num + 1);   // (no bins here: the frame kernel's carve)
+  float *tmp = (float *)A;
+
+  const int g = blockIdx.x * (int)(blockDim.x >> 6) + wv;   // kFeFrames waves per workgroup, fewer for fftN 4096
+  const bool valid = g < Htot;
+  const int gg = valid ? g : Htot - 1;       // idle waves recompute the last frame (same barriers), store nothing
+  const int u = fe_find(hoff, p.nutt, gg);
+  const long long s0 = soff[u] + (long long)(gg - hoff[u]) * p.frameshift;
+  const int16_t *wave = samples + s0;
+  (void)fe_spectrum<false>(p, wave, lane, xr, xi, tmp, misc);
+  if (!valid) return;
+  double *out = mag + (size_t)gg * p.fftN;
+  for (int i = lane; i < p.fftN; i += 64) {
+    const double x = xr[i], y = xi[i];
+    out[i] = sqrt(x * x + y * y);
+  }
+}
+
+// new_SS_calculate()'s sum (ss.c:158-167): spec[i] += |X| is float += double, a rounding chain per index in frame
+// order, so one lane walks the head frames of its (utterance, index); then the float division by the frame count.
+// Consecutive lanes take consecutive indices of one row of mag.
+__global__ void __launch_bounds__(256)
+fe_noise_mean(int fftN, int nutt, const int *__restrict__ hoff, const double *__restrict__ mag, float *__restrict__ noise) {
+  const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= (long long)nutt * fftN) return;
+  const int u = (int)(idx / fftN), i = (int)(idx % fftN);
+  const int h0 = hoff[u], framenum = hoff[u + 1] - h0;
+  const double *col = mag + (size_t)h0 * fftN + i;
+  float acc = 0.0f;
+  for (int t = 0; t < framenum; t++) acc = (float)((double)acc + col[(size_t)t * fftN]);
+  acc /= (float)framenum;
+  noise[idx] = acc;
 }
 
 // NormaliseLogE()'s max: order-free, so a tree (no NaN reaches it: log of a non-negative double)
@@ -446,6 +527,13 @@ struct jamd_frontend {
   char *h_off = nullptr; size_t h_off_cap = 0; hipEvent_t ev_off = nullptr;
   int16_t *d_in = nullptr; size_t in_cap = 0;   // run_host staging
   float *d_out = nullptr; size_t out_cap = 0;
+  // spectral subtraction (jamd_frontend_set_ss)
+  int ss_mode = JAMD_SS_OFF;
+  long long ss_head = 0;                     // -sscalclen in samples
+  float ss_alpha = 0.f, ss_floor = 0.f;
+  float *d_ssload = nullptr;                 // -ssload: the one spectrum [fftN]
+  float *d_noise = nullptr; size_t noise_cap = 0;   // -sscalc: [nutt][fftN]; noise_host staging
+  double *d_mag = nullptr; size_t mag_cap = 0;      // |X| of the head frames [head frames][fftN]
 };
 
 template <typename T>
@@ -604,6 +692,9 @@ void jamd_frontend_destroy(jamd_frontend *f) {
   if (f->d_off) (void)hipFree(f->d_off);
   if (f->d_in) (void)hipFree(f->d_in);
   if (f->d_out) (void)hipFree(f->d_out);
+  if (f->d_ssload) (void)hipFree(f->d_ssload);
+  if (f->d_noise) (void)hipFree(f->d_noise);
+  if (f->d_mag) (void)hipFree(f->d_mag);
   if (f->ev_off) { (void)hipEventSynchronize(f->ev_off); (void)hipEventDestroy(f->ev_off); }
   if (f->h_off) (void)hipHostFree(f->h_off);
   delete f;
@@ -621,7 +712,11 @@ static int fe_upload(jamd_frontend *f, const void *src, size_t bytes, void **dst
 int jamd_frontend_create(jamd_engine *e, const jamd_frontend_desc *d, jamd_frontend **out) {
   if (!e || !d || !out) { jamd_set_error("jamd_frontend_create: NULL argument"); return JAMD_EINVAL; }
   *out = nullptr;
-  if (d->ss) { jamd_set_error("jamd_frontend_create: spectral subtraction (-sscalc / -ssload) is not served"); return JAMD_EINVAL; }
+  if (d->ss) {
+    jamd_set_error("jamd_frontend_create: ss != 0 in the descriptor, which carries none of the parameters of spectral "
+                   "subtraction: leave it 0 and call jamd_frontend_set_ss() on the created object");
+    return JAMD_EINVAL;
+  }
   if (d->realtime) { jamd_set_error("jamd_frontend_create: realtime input / MAP-CMN is not served (buffered front end only)"); return JAMD_EINVAL; }
   if (d->basetype != JAMD_F_MFCC && d->basetype != JAMD_F_FBANK && d->basetype != JAMD_F_MELSPEC) {
     jamd_set_error("jamd_frontend_create: parameter kind %d is not MFCC, FBANK or MELSPEC", d->basetype);
@@ -694,10 +789,11 @@ int jamd_frontend_create(jamd_engine *e, const jamd_frontend_desc *d, jamd_front
   const size_t per_wave = sizeof(double) * ((size_t)w.fftN + (w.nv2 + 1) + (d->fbank_num + 1) + 2);
   f->fpb = per_wave * kFeFrames <= 160u * 1024u ? kFeFrames : per_wave * 2 <= 160u * 1024u ? 2 : 1;
   f->lds = per_wave * f->fpb;
-  if ((rc = jamd_reserve_dyn_lds((const void *)fe_frame_kernel, f->lds, "jamd_frontend_create")) != JAMD_OK) {
-    jamd_frontend_destroy(f);
-    return rc;
-  }
+  for (const void *k : {(const void *)fe_frame_kernel<false>, (const void *)fe_frame_kernel<true>, (const void *)fe_noise_frame})
+    if ((rc = jamd_reserve_dyn_lds(k, f->lds, "jamd_frontend_create")) != JAMD_OK) {
+      jamd_frontend_destroy(f);
+      return rc;
+    }
   *out = f;
   return JAMD_OK;
 }
@@ -716,6 +812,175 @@ int jamd_frontend_frames(const jamd_frontend_desc *d, int64_t nsamples) {
   }
   long long T = fe_frames_raw(*d, nsamples) - (d->splice - 1);
   return T > 0x7fffffff ? 0x7fffffff : (int)T;
+}
+
+int jamd_frontend_fftn(const jamd_frontend *f) { return f ? f->tb.fftN : JAMD_EINVAL; }
+
+int jamd_frontend_ss_default(jamd_frontend_ss *ss) {
+  if (!ss) { jamd_set_error("jamd_frontend_ss_default: ss is NULL"); return JAMD_EINVAL; }
+  // default.c:158-162 with DEF_SSALPHA / DEF_SSFLOOR of mfcc.h:68-69
+  ss->mode = JAMD_SS_OFF; ss->calc_len_ms = 300;
+  ss->alpha = 2.0f; ss->floor = 0.5f;
+  ss->noise = nullptr; ss->noise_len = 0;
+  return JAMD_OK;
+}
+
+int jamd_frontend_set_ss(jamd_frontend *f, const jamd_frontend_ss *ss) {
+  if (!f || !ss) { jamd_set_error("jamd_frontend_set_ss: NULL argument"); return JAMD_EINVAL; }
+  long long head = 0;
+  if (ss->mode == JAMD_SS_CALC) {
+    // m_fusion.c:1409: the head must hold a frame (the reference's product is an int; one past int is refused here)
+    head = (long long)ss->calc_len_ms * f->d.smp_freq / 1000;
+    if (head < f->d.framesize || (long long)ss->calc_len_ms * f->d.smp_freq > 0x7fffffffLL) {
+      jamd_set_error("jamd_frontend_set_ss: head length for SS (%d msec = %lld samples) is shorter than a frame (%d "
+                     "samples), or out of range", ss->calc_len_ms, head, f->d.framesize);
+      return JAMD_EINVAL;
+    }
+  } else if (ss->mode == JAMD_SS_LOAD) {
+    if (!ss->noise || ss->noise_len != f->tb.fftN) {   // Wav2MFCC() refuses ssbuflen != fftN (wav2mfcc-buffer.c:64-69)
+      jamd_set_error("jamd_frontend_set_ss: JAMD_SS_LOAD needs a noise spectrum of fftN = %d values (got %s, length %d)",
+                     f->tb.fftN, ss->noise ? "one" : "NULL", ss->noise_len);
+      return JAMD_EINVAL;
+    }
+    JAMD_HIP(hipSetDevice(f->eng->device));
+    // a buffer of its own per upload: a run queued earlier keeps reading the spectrum it was launched with
+    float *q = nullptr;
+    JAMD_HIP(hipMalloc((void **)&q, sizeof(float) * f->tb.fftN));
+    hipError_t e = hipMemcpy(q, ss->noise, sizeof(float) * f->tb.fftN, hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+      (void)hipFree(q);
+      jamd_set_error("jamd_frontend_set_ss: hipMemcpy failed: %s", hipGetErrorString(e));
+      return JAMD_ENODEV;
+    }
+    if (f->d_ssload) (void)hipFree(f->d_ssload);   // (hipFree waits for the device)
+    f->d_ssload = q;
+  } else if (ss->mode != JAMD_SS_OFF) {
+    jamd_set_error("jamd_frontend_set_ss: unknown mode %d (JAMD_SS_OFF, JAMD_SS_CALC, JAMD_SS_LOAD)", ss->mode);
+    return JAMD_EINVAL;
+  }
+  f->ss_mode = ss->mode; f->ss_head = head;
+  f->ss_alpha = ss->alpha; f->ss_floor = ss->floor;
+  return JAMD_OK;
+}
+
+int jamd_frontend_ss_read(const char *path, float *out, int cap) {
+  if (!path || (cap > 0 && !out)) { jamd_set_error("jamd_frontend_ss_read: NULL argument"); return JAMD_EINVAL; }
+  std::string err;
+  const int n = ssf_read(path, out, cap > 0 ? cap : 0, err);
+  if (n < 0) { jamd_set_error("jamd_frontend_ss_read: %s", err.c_str()); return JAMD_EINVAL; }
+  return n;
+}
+
+int jamd_frontend_ss_write(const char *path, const float *noise, int n) {
+  if (!path || !noise || n < 0) { jamd_set_error("jamd_frontend_ss_write: NULL argument or n < 0"); return JAMD_EINVAL; }
+  std::string err;
+  if (ssf_write(path, noise, n, err) != 0) { jamd_set_error("jamd_frontend_ss_write: %s", err.c_str()); return JAMD_EINVAL; }
+  return JAMD_OK;
+}
+
+// The offsets go up through a pinned buffer that is rewritten only once the copy that read it is done.
+// blob = soff (int64 [nutt + 1]) followed by ntab int32 tables [nutt + 1].
+static int fe_put_offsets(jamd_frontend *f, hipStream_t st, const int64_t *sample_off, int nutt,
+                          std::initializer_list<const std::vector<int> *> tabs) {
+  const size_t offb = sizeof(long long) * (nutt + 1) + tabs.size() * sizeof(int) * (nutt + 1);
+  int rc;
+  if ((rc = fe_reserve(&f->d_off, &f->off_cap, offb)) != JAMD_OK) return rc;
+  if (f->ev_off) JAMD_HIP(hipEventSynchronize(f->ev_off));
+  else JAMD_HIP(hipEventCreateWithFlags(&f->ev_off, hipEventDisableTiming));
+  if (f->h_off_cap < offb) {
+    if (f->h_off) JAMD_HIP(hipHostFree(f->h_off));
+    f->h_off = nullptr; f->h_off_cap = 0;
+    JAMD_HIP(hipHostMalloc((void **)&f->h_off, offb, hipHostMallocDefault));
+    f->h_off_cap = offb;
+  }
+  memcpy(f->h_off, sample_off, sizeof(long long) * (nutt + 1));
+  char *q = f->h_off + sizeof(long long) * (nutt + 1);
+  for (const std::vector<int> *t : tabs) { memcpy(q, t->data(), sizeof(int) * (nutt + 1)); q += sizeof(int) * (nutt + 1); }
+  JAMD_HIP(hipMemcpyAsync(f->d_off, f->h_off, offb, hipMemcpyHostToDevice, st));
+  JAMD_HIP(hipEventRecord(f->ev_off, st));
+  return JAMD_OK;
+}
+
+// Head frames of every utterance (head_samples <= 0: the whole utterance) -> hoff [nutt + 1]; false with the error
+// set when sample_off is not in order or a head holds no full frame.
+static bool fe_head_frames(const jamd_frontend *f, const char *who, const int64_t *sample_off, int nutt,
+                           long long head_samples, std::vector<int> &hoff) {
+  hoff.assign(nutt + 1, 0);
+  long long Hall = 0;
+  for (int u = 0; u < nutt; u++) {
+    if (sample_off[u] < 0 || sample_off[u + 1] < sample_off[u]) {
+      jamd_set_error("%s: sample_off is not non-decreasing from 0 at utterance %d", who, u);
+      return false;
+    }
+    long long n = sample_off[u + 1] - sample_off[u];
+    if (head_samples > 0 && head_samples < n) n = head_samples;
+    const long long H = fe_frames_raw(f->d, n);
+    if (H < 1) {
+      jamd_set_error("%s: the head of utterance %d (%lld samples) holds no full frame", who, u, n);
+      return false;
+    }
+    hoff[u] = (int)Hall;
+    Hall += H;
+    if (Hall > 0x7fffffffLL) { jamd_set_error("%s: batch too large (%lld head frames)", who, Hall); return false; }
+  }
+  hoff[nutt] = (int)Hall;
+  return true;
+}
+
+// fe_noise_frame + fe_noise_mean over the head frames d_hoff describes -> dev_noise [nutt][fftN]
+static int fe_noise_launch(jamd_frontend *f, hipStream_t st, const int16_t *dev_samples, const long long *d_soff,
+                           const int *d_hoff, int nutt, int Htot, float *dev_noise) {
+  int rc;
+  if ((rc = fe_reserve(&f->d_mag, &f->mag_cap, (size_t)Htot * f->tb.fftN)) != JAMD_OK) return rc;
+  FeParams p = f->p;
+  p.nutt = nutt;
+  hipLaunchKernelGGL(fe_noise_frame, dim3((Htot + f->fpb - 1) / f->fpb), dim3(64 * f->fpb), f->lds, st, p, dev_samples,
+                     d_soff, d_hoff, Htot, f->d_mag);
+  JAMD_HIP(hipGetLastError());
+  const long long nn = (long long)nutt * f->tb.fftN;
+  hipLaunchKernelGGL(fe_noise_mean, dim3((unsigned)((nn + 255) / 256)), dim3(256), 0, st, f->tb.fftN, nutt, d_hoff,
+                     f->d_mag, dev_noise);
+  JAMD_HIP(hipGetLastError());
+  return JAMD_OK;
+}
+
+int jamd_frontend_noise_dev(jamd_frontend *f, const int16_t *dev_samples, const int64_t *sample_off, int nutt,
+                            int64_t head_samples, float *dev_noise, void *stream) {
+  if (!f || !dev_samples || !sample_off || !dev_noise || nutt < 1) {
+    jamd_set_error("jamd_frontend_noise_dev: NULL argument or nutt < 1");
+    return JAMD_EINVAL;
+  }
+  if ((long long)nutt * f->tb.fftN > 0x7fffffffLL) { jamd_set_error("jamd_frontend_noise_dev: batch too large"); return JAMD_EINVAL; }
+  std::vector<int> hoff;
+  if (!fe_head_frames(f, "jamd_frontend_noise_dev", sample_off, nutt, head_samples, hoff)) return JAMD_EINVAL;
+  JAMD_HIP(hipSetDevice(f->eng->device));
+  hipStream_t st = jamd_stream(f->eng, stream);
+  int rc;
+  if ((rc = fe_put_offsets(f, st, sample_off, nutt, {&hoff})) != JAMD_OK) return rc;
+  const long long *d_soff = (const long long *)f->d_off;
+  return fe_noise_launch(f, st, dev_samples, d_soff, (const int *)(d_soff + nutt + 1), nutt, hoff[nutt], dev_noise);
+}
+
+int jamd_frontend_noise_host(jamd_frontend *f, const int16_t *samples, const int64_t *sample_off, int nutt,
+                             int64_t head_samples, float *noise) {
+  if (!f || !samples || !sample_off || !noise || nutt < 1) {
+    jamd_set_error("jamd_frontend_noise_host: NULL argument or nutt < 1");
+    return JAMD_EINVAL;
+  }
+  if ((long long)nutt * f->tb.fftN > 0x7fffffffLL) { jamd_set_error("jamd_frontend_noise_host: batch too large"); return JAMD_EINVAL; }
+  std::vector<int> hoff;
+  if (!fe_head_frames(f, "jamd_frontend_noise_host", sample_off, nutt, head_samples, hoff)) return JAMD_EINVAL;
+  JAMD_HIP(hipSetDevice(f->eng->device));
+  int rc;
+  const size_t ns = (size_t)sample_off[nutt], nn = (size_t)nutt * f->tb.fftN;
+  if ((rc = fe_reserve(&f->d_in, &f->in_cap, ns > 0 ? ns : 1)) != JAMD_OK) return rc;
+  if ((rc = fe_reserve(&f->d_noise, &f->noise_cap, nn)) != JAMD_OK) return rc;
+  hipStream_t st = f->eng->stream;
+  JAMD_HIP(hipMemcpyAsync(f->d_in, samples, ns * sizeof(int16_t), hipMemcpyHostToDevice, st));
+  if ((rc = jamd_frontend_noise_dev(f, f->d_in, sample_off, nutt, head_samples, f->d_noise, st)) != JAMD_OK) return rc;
+  JAMD_HIP(hipMemcpyAsync(noise, f->d_noise, nn * sizeof(float), hipMemcpyDeviceToHost, st));
+  JAMD_HIP(hipStreamSynchronize(st));
+  return JAMD_OK;
 }
 
 int jamd_frontend_run_dev(jamd_frontend *f, const int16_t *dev_samples, const int64_t *sample_off, int nutt,
@@ -746,37 +1011,42 @@ int jamd_frontend_run_dev(jamd_frontend *f, const int16_t *dev_samples, const in
     }
   }
   foff[nutt] = (int)Tall; ooff[nutt] = (int)Tout;
+  std::vector<int> hoff;                     // -sscalc: the head frames (every utterance holds a frame, so its head does)
+  if (f->ss_mode == JAMD_SS_CALC) {
+    if ((long long)nutt * f->tb.fftN > 0x7fffffffLL) { jamd_set_error("jamd_frontend_run_dev: batch too large"); return JAMD_EINVAL; }
+    if (!fe_head_frames(f, "jamd_frontend_run_dev", sample_off, nutt, f->ss_head, hoff)) return JAMD_EINVAL;
+  }
   JAMD_HIP(hipSetDevice(f->eng->device));
   hipStream_t st = jamd_stream(f->eng, stream);
   int rc;
   if ((rc = fe_reserve(&f->d_stat, &f->stat_cap, (size_t)Tall * d.baselen)) != JAMD_OK) return rc;
   if ((rc = fe_reserve(&f->d_feat, &f->feat_cap, (size_t)Tall * d.veclen)) != JAMD_OK) return rc;
   if ((rc = fe_reserve(&f->d_ms, &f->ms_cap, (size_t)nutt * (2 * d.veclen + 1))) != JAMD_OK) return rc;
-  const size_t offb = sizeof(long long) * (nutt + 1) + 2 * sizeof(int) * (nutt + 1);
-  if ((rc = fe_reserve(&f->d_off, &f->off_cap, offb)) != JAMD_OK) return rc;
-  // the offsets go up through a pinned buffer that is rewritten only once the copy that read it is done
-  if (f->ev_off) JAMD_HIP(hipEventSynchronize(f->ev_off));
-  else JAMD_HIP(hipEventCreateWithFlags(&f->ev_off, hipEventDisableTiming));
-  if (f->h_off_cap < offb) {
-    if (f->h_off) JAMD_HIP(hipHostFree(f->h_off));
-    f->h_off = nullptr; f->h_off_cap = 0;
-    JAMD_HIP(hipHostMalloc((void **)&f->h_off, offb, hipHostMallocDefault));
-    f->h_off_cap = offb;
-  }
-  memcpy(f->h_off, sample_off, sizeof(long long) * (nutt + 1));
-  memcpy(f->h_off + sizeof(long long) * (nutt + 1), foff.data(), sizeof(int) * (nutt + 1));
-  memcpy(f->h_off + sizeof(long long) * (nutt + 1) + sizeof(int) * (nutt + 1), ooff.data(), sizeof(int) * (nutt + 1));
-  JAMD_HIP(hipMemcpyAsync(f->d_off, f->h_off, offb, hipMemcpyHostToDevice, st));
-  JAMD_HIP(hipEventRecord(f->ev_off, st));
+  if (f->ss_mode == JAMD_SS_CALC) rc = fe_put_offsets(f, st, sample_off, nutt, {&foff, &ooff, &hoff});
+  else rc = fe_put_offsets(f, st, sample_off, nutt, {&foff, &ooff});
+  if (rc != JAMD_OK) return rc;
   const long long *d_soff = (const long long *)f->d_off;
   const int *d_foff = (const int *)(d_soff + nutt + 1), *d_ooff = d_foff + nutt + 1;
   float *d_mean = f->d_ms, *d_sd = d_mean + (size_t)nutt * d.veclen, *d_emax = d_sd + (size_t)nutt * d.veclen;
 
   FeParams p = f->p;
   p.nutt = nutt;
-  const int T = (int)Tall;
-  hipLaunchKernelGGL(fe_frame_kernel, dim3((T + f->fpb - 1) / f->fpb), dim3(64 * f->fpb), f->lds, st, p,
-                     dev_samples, d_soff, d_foff, T, f->d_stat);
+  const int T = (int)Tall, w_fftN = f->tb.fftN;
+  if (f->ss_mode == JAMD_SS_OFF) {
+    hipLaunchKernelGGL(fe_frame_kernel<false>, dim3((T + f->fpb - 1) / f->fpb), dim3(64 * f->fpb), f->lds, st, p,
+                       dev_samples, d_soff, d_foff, T, f->d_stat, (const float *)nullptr, 0, 0.0f, 0.0f);
+  } else {
+    const float *d_noise = f->d_ssload;      // -ssload: one spectrum for every utterance
+    if (f->ss_mode == JAMD_SS_CALC) {        // -sscalc: the spectrum of every utterance's head first, on this stream
+      if ((rc = fe_reserve(&f->d_noise, &f->noise_cap, (size_t)nutt * w_fftN)) != JAMD_OK) return rc;
+      if ((rc = fe_noise_launch(f, st, dev_samples, d_soff, d_ooff + nutt + 1, nutt, hoff[nutt], f->d_noise)) != JAMD_OK)
+        return rc;
+      d_noise = f->d_noise;
+    }
+    hipLaunchKernelGGL(fe_frame_kernel<true>, dim3((T + f->fpb - 1) / f->fpb), dim3(64 * f->fpb), f->lds, st, p,
+                       dev_samples, d_soff, d_foff, T, f->d_stat, d_noise, f->ss_mode == JAMD_SS_CALC ? w_fftN : 0,
+                       f->ss_alpha, f->ss_floor);
+  }
   JAMD_HIP(hipGetLastError());
   if (p.enormal && p.energy) {
     hipLaunchKernelGGL(fe_emax_kernel, dim3(nutt), dim3(256), 0, st, p, f->d_stat, d_foff, d_emax);

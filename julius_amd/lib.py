@@ -57,6 +57,15 @@ class FrontendDesc(C.Structure):
         ("ss", C.c_int), ("realtime", C.c_int)]
 
 
+SS_OFF, SS_CALC, SS_LOAD = 0, 1, 2
+
+
+class FrontendSS(C.Structure):
+    """jamd_frontend_ss (include/julius_amd.h): -sscalc / -sscalclen / -ssload / -ssalpha / -ssfloor."""
+    _fields_ = [("mode", C.c_int), ("calc_len_ms", C.c_int), ("alpha", C.c_float), ("floor", C.c_float),
+                ("noise", C.c_void_p), ("noise_len", C.c_int)]
+
+
 _lib = None
 
 
@@ -171,6 +180,13 @@ def load():
         "jamd_frontend_frames": (ci, [P(FrontendDesc), C.c_int64]),
         "jamd_frontend_run_dev": (ci, [vp, vp, vp, ci, vp, vp, vp]),
         "jamd_frontend_run_host": (ci, [vp, vp, vp, ci, vp, vp]),
+        "jamd_frontend_ss_default": (ci, [P(FrontendSS)]),
+        "jamd_frontend_set_ss": (ci, [vp, P(FrontendSS)]),
+        "jamd_frontend_fftn": (ci, [vp]),
+        "jamd_frontend_noise_dev": (ci, [vp, vp, vp, ci, C.c_int64, vp, vp]),
+        "jamd_frontend_noise_host": (ci, [vp, vp, vp, ci, C.c_int64, vp]),
+        "jamd_frontend_ss_read": (ci, [C.c_char_p, vp, ci]),
+        "jamd_frontend_ss_write": (ci, [C.c_char_p, vp, ci]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -798,6 +814,22 @@ def param_kind(name: str) -> int:
     return code
 
 
+def ss_read(path) -> np.ndarray:
+    """A noise spectrum file of mkss / -ssload (big-endian count, then big-endian floats) -> float32 [count]."""
+    n = load().jamd_frontend_ss_read(str(path).encode(), None, 0)
+    if n < 0:
+        raise JamdError(f"jamd_frontend_ss_read failed ({n}): {load().jamd_last_error().decode()}")
+    out = np.zeros(n, np.float32)
+    if load().jamd_frontend_ss_read(str(path).encode(), out.ctypes.data, n) != n:
+        raise JamdError(f"jamd_frontend_ss_read failed: {load().jamd_last_error().decode()}")
+    return out
+
+
+def ss_write(path, noise):
+    noise = _f32(noise).ravel()
+    _check(load().jamd_frontend_ss_write(str(path).encode(), noise.ctypes.data, len(noise)), "jamd_frontend_ss_write")
+
+
 class Frontend:
     """Audio front end (jamd_frontend): Wav2MFCC() of libsent/src/wav2mfcc/wav2mfcc-buffer.c plus the
     splicing of libjulius/src/wav2mfcc.c, on the device.  int16 PCM in, features [T][veclen * splice] out."""
@@ -812,6 +844,7 @@ class Frontend:
         _check(load().jamd_frontend_create(eng.h, C.byref(desc), C.byref(h)), "jamd_frontend_create")
         self.h = h
         self.veclen = load().jamd_frontend_veclen(h)
+        self.fftn = load().jamd_frontend_fftn(h)
 
     @staticmethod
     def desc_for(kind, vecsize: int, htkconf=None, **fields) -> FrontendDesc:
@@ -854,6 +887,29 @@ class Frontend:
         _check(load().jamd_frontend_run_host(self.h, samples.ctypes.data, off.ctypes.data, len(utts),
                                              out.ctypes.data, foff.ctypes.data), "jamd_frontend_run_host")
         return out, foff
+
+    def set_ss(self, mode, calc_len_ms: int = 300, alpha: float = 2.0, floor: float = 0.5, noise=None):
+        """Spectral subtraction for every later run: SS_CALC (-sscalc, head of calc_len_ms per utterance), SS_LOAD
+        (-ssload, `noise` float32 [fftn]) or SS_OFF.  A refused call raises and leaves the object as it was."""
+        mode = {"off": SS_OFF, "calc": SS_CALC, "load": SS_LOAD}.get(mode, mode)
+        nz = _f32(noise).ravel() if noise is not None else None
+        ss = FrontendSS(int(mode), int(calc_len_ms), float(alpha), float(floor),
+                        nz.ctypes.data if nz is not None else None, len(nz) if nz is not None else 0)
+        _check(load().jamd_frontend_set_ss(self.h, C.byref(ss)), "jamd_frontend_set_ss")
+
+    def noise_host(self, utts, head_samples: int = 0):
+        """new_SS_calculate() over the first min(head_samples, length) samples of every utterance (0: all of it):
+        list of int16 arrays -> float32 [nutt][fftn]."""
+        samples, off = self._pack(utts)
+        out = np.zeros((len(utts), self.fftn), np.float32)
+        _check(load().jamd_frontend_noise_host(self.h, samples.ctypes.data, off.ctypes.data, len(utts),
+                                               int(head_samples), out.ctypes.data), "jamd_frontend_noise_host")
+        return out
+
+    def noise_dev(self, dev_samples: int, sample_off, dev_noise: int, head_samples: int = 0, stream: int = 0):
+        off = np.ascontiguousarray(sample_off, dtype=np.int64)
+        _check(load().jamd_frontend_noise_dev(self.h, dev_samples, off.ctypes.data, len(off) - 1, int(head_samples),
+                                              dev_noise, stream or None), "jamd_frontend_noise_dev")
 
     def run_dev(self, dev_samples: int, sample_off, dev_out: int, stream: int = 0):
         """Device samples and features; sample_off host int64 [nutt + 1].  Returns frame_off [nutt + 1]."""

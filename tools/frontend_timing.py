@@ -1,12 +1,16 @@
 """Device audio front end (jamd_frontend_run_dev) on the C3 batch shape -- 512 ragged utterances, 727 200
 frames at 16 kHz / 10 ms -- beside the compiled reference's Wav2MFCC() on one host core of the same machine.
 
-  python tools/frontend_timing.py [--reps 10] [--ref-frames 30000] [--json out.json]
+  python tools/frontend_timing.py [--reps 10] [--ref-frames 30000] [--ss off|calc|load] [--json out.json]
 
 Device time: wall clock of run_dev + stream sync (median of --reps, after a warm-up), samples already on the
 device.  Reference: the Wav2MFCC() call alone of oracle/_ref/libjref.so over utterances of the same length distribution
 (--ref-frames frames in all), per frame, scaled to the batch.  Both kinds of the issue: MFCC_E_D_A_Z (39) and
-MFCC_E_D_N_Z (25)."""
+MFCC_E_D_N_Z (25).
+
+--ss calc runs the batch under -sscalc (a 300 ms head per utterance: two more kernels in front of the frame kernel),
+--ss load under -ssload with one spectrum for all (taken from the first utterance); alpha 2.0, floor 0.5.  The default,
+off, is the run without spectral subtraction.  The reference is not timed under --ss calc / load."""
 import argparse
 import json
 import sys
@@ -43,15 +47,20 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--ref-frames", type=int, default=30000)
+    ap.add_argument("--ss", choices=("off", "calc", "load"), default="off")
     ap.add_argument("--json")
     a = ap.parse_args()
     eng = lib.Engine(0)
     utts = batch()
     samples, off = lib.Frontend._pack(utts)
     d_in = lib.DevBuf(eng, samples.nbytes).upload(samples)
-    out = {"utterances": NUTT, "frames": FRAMES, "samples": int(off[-1]), "kinds": {}}
+    out = {"utterances": NUTT, "frames": FRAMES, "samples": int(off[-1]), "ss": a.ss, "kinds": {}}
     for kind, vs in (("MFCC_E_D_A_Z", 39), ("MFCC_E_D_N_Z", 25)):
         fe = lib.Frontend.from_kind(eng, kind, vs)
+        if a.ss == "calc":
+            fe.set_ss(lib.SS_CALC)
+        elif a.ss == "load":
+            fe.set_ss(lib.SS_LOAD, noise=fe.noise_host(utts[:1])[0])
         d_out = lib.DevBuf(eng, 4 * FRAMES * fe.veclen)
         foff = fe.run_dev(d_in.ptr, off, d_out.ptr)
         eng.sync()
@@ -66,6 +75,8 @@ def main():
         rec = {"device_ms_per_batch": round(dev_ms, 3), "device_ms_min": round(1e3 * min(ts), 3),
                "device_rtf_inv": round(FRAMES * 0.01 / (dev_ms / 1e3), 1)}
         try:
+            if a.ss != "off":
+                raise FileNotFoundError("the reference is timed without spectral subtraction only")
             from oracle import pyoracle
             from frontendref import RefFrontend
             rf = RefFrontend(pyoracle.Ref())
