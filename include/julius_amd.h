@@ -641,7 +641,13 @@ int  jamd_beam_prune_info(jamd_beam *b, int *sweep_rounds, int *sweep_us, int *s
  *   [4] upward, sweep gave the frame to the extraction loop [5] downward, closed form (sweep + residual-heap replay)
  *   [6] extraction loop itself (pipelined / serial)        [7] sweep rounds, total
  * and the work of the frames (sums over the frames): [8] tokens created, [9] survivors visited, [10] word ends among them,
- * [11] frames; [12..15] reserved.  reset != 0 clears them.  Diagnostic. */
+ * [11] frames; [12] multipath frame: frames whose new tokens exceeded the beam (the mid-frame sort really sorted);
+ * the lane split of the state-set reductions (outprob_cd() inside the frame, csrc/beam_exact.hip step C):
+ *   [13] frames that ran two lanes per set                 [14] frames that ran one lane per set
+ *   [15] state-set reductions, summed over the frames
+ * (four-lane frames = [11] - [13] - [14]; the N-gram's initial token is scored before the frame loop and is in none of
+ * [8..15]).  The multipath frame reduces a set on one lane per token and has no split:
+ * it leaves [13..15] at 0.  reset != 0 clears them.  Diagnostic. */
 int  jamd_beam_prune_stats(jamd_beam *b, int utt, int stats[16], int reset);
 int  jamd_beam_results(jamd_beam *b, jamd_pass1_result *out, int nutt);
 /* Word trellis of utterance u in emission order (last_tre indexes the same

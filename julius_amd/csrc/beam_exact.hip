@@ -450,6 +450,9 @@ beam_exact_kernel(XKArgs ka_, const float *__restrict__ scores, int S, const int
       const int n_set = uni(sh.n_arc);
       const int lps = n_set <= NT / 4 ? 4 : (n_set <= NT / 2 ? 2 : 1), lsh = lps == 4 ? 2 : (lps == 2 ? 1 : 0);
       const int sub = tid & (lps - 1), lane = tid & 63;
+      // the lane split (jamd_beam_prune_stats() [13..15]): LDS adds that return nothing, from the thread whose wave has the
+      // fewest items below (thread 0's has the most, and the other [8..11] updates)
+      if (tid == NT - 1) { atomicAdd(&sh.pst[15], n_set); if (lps != 4) atomicAdd(&sh.pst[lps == 2 ? 13 : 14], 1); }
       for (int q0 = 0; q0 < n_set; q0 += NT >> lsh) {
         const int q = q0 + (tid >> lsh);
         const bool act = q < n_set;

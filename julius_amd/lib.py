@@ -740,7 +740,13 @@ class Beam:
         return r.value
 
     def prune_stats(self, utt=0, reset=False):
-        """Frames of utterance `utt` by the path their rank pruning step took (jamd_beam_prune_stats)."""
+        """Counters of utterance `utt` in the exact-order kernel since the work area was created or they were last
+        reset (jamd_beam_prune_stats): [0..7] frames by the path their rank pruning step took, [8..11] work sums
+        (tokens created, survivors visited, word ends, frames), [12] multipath frames that sorted mid-frame, and the
+        lane split of the state-set reductions: [13] frames that ran two lanes per set, [14] frames that ran one,
+        [15] reductions summed over the frames (four-lane frames = [11] - [13] - [14]; a multipath lexicon leaves
+        [13..15] at 0).  The frames are the turns of the kernel's frame loop: under an N-gram the initial token is
+        scored before it, so T input frames count as T - 1."""
         st = np.zeros(16, np.int32)
         _check(load().jamd_beam_prune_stats(self.h, utt, st.ctypes.data, 1 if reset else 0), "jamd_beam_prune_stats")
         return [int(x) for x in st]

@@ -98,6 +98,15 @@ static float iw_prob(const jamd_lexicon_desc *lx, int lastword, int stid)
   return jo_bigram_prob(lx, lx->wton[lastword], lx->wton[w]) + lx->cprob[w];
 }
 
+/* Test tooling: an optional tap on outprob_style().  While set, calls[t] counts the jo_outprob_cd() calls of frame t
+ * (the state-set reductions the frame needs) and big[t] those on sets of more than 32 members; both arrays hold `frames`
+ * ints and are the caller's.  jo_beam_cd_tap(NULL, NULL, 0) removes it. */
+static int *jo_cd_calls = NULL, *jo_cd_big = NULL, jo_cd_frames = 0;
+void jo_beam_cd_tap(int *calls, int *big, int frames)
+{
+  jo_cd_calls = calls; jo_cd_big = big; jo_cd_frames = (calls && big) ? frames : 0;
+}
+
 /* ---- acoustic score of a node: outprob_style(), libjulius/src/outprob_style.c:354 */
 static float outprob_style(const beam *b, int node, int last_wid, int t)
 {
@@ -113,6 +122,10 @@ static float outprob_style(const beam *b, int node, int last_wid, int t)
   }
   if (ent >= 0) return row[ent];
   ent = ~ent;
+  if (t < jo_cd_frames) {
+    jo_cd_calls[t]++;
+    if (lx->set_off[ent + 1] - lx->set_off[ent] > 32) jo_cd_big[t]++;
+  }
   return jo_outprob_cd(row, lx->set_states + lx->set_off[ent], lx->set_off[ent + 1] - lx->set_off[ent],
                        lx->cdset_method, lx->cdmax_num);
 }

@@ -167,9 +167,11 @@ class Oracle:
                 out[t, i] = self.lib.jo_outprob_cd(_p(row), _p(sub), len(sub), method, nbest)
         return out
 
-    def beam_pass1(self, lex, scores, beam_width, score_pruning_width=-1.0, atom_cap=None):
+    def beam_pass1(self, lex, scores, beam_width, score_pruning_width=-1.0, atom_cap=None, counts=False):
         """First pass over a [T][S] state score matrix.  Returns (atoms structured
-        array in emission order, pass-1 word sequence, pass-1 score, rc, died_at)."""
+        array in emission order, pass-1 word sequence, pass-1 score, rc, died_at).
+        counts=True appends (calls, big): per frame, the state-set reductions (jo_outprob_cd() calls)
+        the frame needed and those of them on sets of more than 32 members (int32 [T] each)."""
         from julius_amd import lexblob
         lib = self.lib
         lib.jo_beam_pass1.restype = C.c_int
@@ -184,9 +186,18 @@ class Oracle:
         natom, wnum, died = C.c_int(), C.c_int(), C.c_int()
         score = C.c_float()
         wseq = np.zeros(4096, np.int32)
-        rc = lib.jo_beam_pass1(C.byref(d), _p(sc), T, S, beam_width, score_pruning_width, _p(atoms), cap,
-                               C.byref(natom), _p(wseq), len(wseq), C.byref(wnum), C.byref(score), C.byref(died))
-        return atoms[:natom.value].copy(), wseq[:wnum.value].copy(), float(score.value), rc, died.value
+        calls, big = np.zeros(T, np.int32), np.zeros(T, np.int32)
+        lib.jo_beam_cd_tap.restype = None
+        lib.jo_beam_cd_tap.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+        if counts:
+            lib.jo_beam_cd_tap(_p(calls), _p(big), T)
+        try:
+            rc = lib.jo_beam_pass1(C.byref(d), _p(sc), T, S, beam_width, score_pruning_width, _p(atoms), cap,
+                                   C.byref(natom), _p(wseq), len(wseq), C.byref(wnum), C.byref(score), C.byref(died))
+        finally:
+            lib.jo_beam_cd_tap(None, None, 0)
+        out = (atoms[:natom.value].copy(), wseq[:wnum.value].copy(), float(score.value), rc, died.value)
+        return out + (calls, big) if counts else out
 
     def sort_token_no_order(self, scores, beam_width):
         """beam.c:1492: visiting order (token ids) of the next frame for tokens with these scores in creation order."""
