@@ -672,7 +672,9 @@ int  jamd_beam_trellis(jamd_beam *b, int utt, jamd_trellis_atom *atoms, int cap,
  * behind this library):
  *   - ss != 0 in the descriptor: the descriptor carries none of the parameters of spectral subtraction,
  *     which is switched on with jamd_frontend_set_ss();
- *   - realtime input and MAP-CMN (the pipelined front end of wav2mfcc-pipe.c): realtime != 0;
+ *   - realtime != 0: the descriptor of the buffered front end stays the buffered one.  The pipelined front end of
+ *     wav2mfcc-pipe.c (microphone, socket, -realtime: MAP-CMN, energy by the previous maximum, cyclic deltas) is an
+ *     object of its own made from a created jamd_frontend: jamd_frontend_live_create() below;
  *   - kinds other than MFCC, FBANK and MELSPEC, FBANK / MELSPEC with _E or _0 (WMP_calc() leaves
  *     those slots unwritten), _N without _E and _D, _A without _D. */
 #define JAMD_F_MFCC     6
@@ -772,6 +774,75 @@ int  jamd_frontend_noise_host(jamd_frontend *f, const int16_t *samples, const in
  * returns the count in the file (copies min(count, cap)); a file shorter than its count is refused. */
 int  jamd_frontend_ss_read (const char *path, float *out, int cap);
 int  jamd_frontend_ss_write(const char *path, const float *noise, int n);
+
+/* ---- live-input front end: whole segments of many independent channels per call ----------------
+ * What the reference computes for a microphone, a socket or -realtime, bit-identical: the vectors RealTimeMFCC()
+ * (libjulius/src/realtime-1stpass.c:496-602) and the flush loop of RealTimeParam() (:1215-1304, splicing included)
+ * store into mfcc->param, from the state reset_mfcc() / CMN_realtime_prepare() leave.  They differ from the buffered
+ * features in every normalised element: the cepstral mean is MAP over the frames seen so far, seeded from earlier
+ * segments (CMN_realtime(), wav2mfcc-pipe.c:342-399); the energy is normalised by the previous segment's maximum
+ * (energy_max_normalize()); the deltas go through the cyclic buffers in float (WMP_deltabuf_calc()); the window is
+ * framesize + 1 samples.  The object is made from a created jamd_frontend, whose tables, frame kernel, spectral
+ * subtraction (JAMD_SS_LOAD / JAMD_SS_OFF) and device scratch it shares: the one-stream rule of
+ * jamd_frontend_run_dev() covers the parent and every live object made from it together.  The state the reference
+ * carries from one utterance to the next (ENERGYWork.max, CMNWork) is kept per channel on the device.
+ * Which julius option is which call: INTEGRATION.md.
+ *
+ * NOT SERVED: chunked input inside a segment (one call = one whole segment per channel); _N together with _A
+ * (refused by _create: the reference's two loops disagree on it, realtime-1stpass.c:1233-1241 against :583-587);
+ * JAMD_SS_CALC on the parent (refused by _run: a live segment has no head known in advance); frameshift beyond the
+ * window; gzipped -cmnload files. */
+typedef struct {
+  int   map_cmn;                 /* 1 = MAP-CMN, 0 = -cmnstatic (CMNWork.do_map)                          */
+  float map_weight;              /* -cmnmapweight                                                         */
+  const float *cmean_init;       /* -cmnload, for every channel: [veclen] or NULL (cmean_init_set FALSE)  */
+  const float *cvar_init;        /* [veclen] or NULL; read only when the kind has cvn, then needed        */
+} jamd_frontend_live_desc;
+typedef struct jamd_frontend_live jamd_frontend_live;
+#define JAMD_LIVE_CMEAN_SET 1    /* flags of _state_get: CMNWork.cmean_init_set                           */
+#define JAMD_LIVE_LOADED    2    /*                      CMNWork.loaded_from_file                         */
+
+int  jamd_frontend_live_default(jamd_frontend_live_desc *d);          /* 1, 100.0 (default.c:153-156), NULL, NULL */
+/* nchan channels, each with the state of a fresh start (energy maximum 5.0, no history).  `f` must outlive it. */
+int  jamd_frontend_live_create(jamd_frontend *f, const jamd_frontend_live_desc *d, int nchan, jamd_frontend_live **out);
+void jamd_frontend_live_destroy(jamd_frontend_live *l);
+/* Host only.  Rows one segment of nsamples samples yields.  Not jamd_frontend_frames(): the live window is
+ * framesize + 1 samples (realtime-1stpass.c:290), so Tb = (n - framesize - 1) / frameshift + 1 base frames for
+ * n >= framesize + 1; the flush loop ends at the first WMP_deltabuf_flush() that finds its slot empty, so with _D a
+ * segment of Tb < delWin emits nothing, and with _A neither does one of fewer than accWin delta vectors; splice takes
+ * splice - 1 more.  Never negative.  (Where the delta vectors of the flush loop meet an acceleration buffer still in
+ * its delay, Tb < delWin + accWin, the reference advances its frame counter without storing a vector; the rows
+ * counted and returned here are the vectors it does store.) */
+int  jamd_frontend_live_frames(const jamd_frontend_desc *d, int64_t nsamples);
+/* One segment per channel: channel c gets samples [sample_off[c], sample_off[c+1]) of dev_samples (host offsets
+ * [nchan + 1]).  Output as jamd_frontend_run_dev(): rows back to back in dev_out, host row offsets [nchan + 1] in
+ * frame_off (may be NULL).  A channel without samples is idle: no rows, its state untouched.  A channel whose segment
+ * yields no row is no error: it reports none, the maximum of its base frames' energies still becomes the next
+ * segment's, and a commit leaves it alone (CMN_realtime_update() returns when now.framenum is 0).  Every run starts
+ * from CMN_realtime_prepare(): two runs without a commit between them both start from the same initial mean. */
+int  jamd_frontend_live_run_dev (jamd_frontend_live *l, const int16_t *dev_samples, const int64_t *sample_off,
+                                 float *dev_out, int *frame_off, void *stream);
+int  jamd_frontend_live_run_host(jamd_frontend_live *l, const int16_t *samples, const int64_t *sample_off, float *out,
+                                 int *frame_off);
+/* CMN_realtime_update(wrk, param) (wav2mfcc-pipe.c:407-479) for the channels whose byte of `update` ([nchan], host) is
+ * non-zero; NULL = every channel.  -cmnnoupdate: never call it; an input that was rejected
+ * (realtime-1stpass.c:1416-1442): a zero byte.  Queued on `stream` behind the run it belongs to.  It is that call
+ * and nothing more: it works on the channel's last segment, so give a channel that was idle in the run a zero byte
+ * (a non-zero one enters its last segment into the history again, as a second CMN_realtime_update() would).  The energy maximum
+ * is not its business: it moves at the next run, where energy_max_prepare() sits. */
+int  jamd_frontend_live_commit(jamd_frontend_live *l, const unsigned char *update, void *stream);
+/* The state of one channel after everything queued so far (both wait for the device): cmean_init / cvar_init [veclen]
+ * (cvar only meaningful with cvn), ENERGYWork.max, JAMD_LIVE_* flags; any pointer may be NULL.  _state_set is -cmnload
+ * on that channel (cvar needed when the kind has cvn): as CMN_load_from_file() it also stops the variance updates. */
+int  jamd_frontend_live_state_get(jamd_frontend_live *l, int chan, float *cmean, float *cvar, float *emax, int *flags);
+int  jamd_frontend_live_state_set(jamd_frontend_live *l, int chan, const float *cmean, const float *cvar);
+/* host only: the -cmnload / -cmnsave file.  read takes both forms of CMN_load_from_file() (:514-652): the ASCII
+ * <CEPSNORM> form, whose <MEAN> has veclen or mfcc_dim (cepstra + c0) entries and whose <VARIANCE> is optional, and
+ * the old big-endian binary form (whose variance is read when want_var != 0).  Returns 1 when a variance was read, 0
+ * for a mean alone, JAMD_EINVAL where the reference refuses the file.  write is CMN_save_to_file(), byte for byte;
+ * cvar == NULL writes no variance. */
+int  jamd_frontend_cmn_read (const char *path, int veclen, int mfcc_dim, int want_var, float *cmean, float *cvar);
+int  jamd_frontend_cmn_write(const char *path, int veclen, const float *cmean, const float *cvar);
 
 #ifdef __cplusplus
 }

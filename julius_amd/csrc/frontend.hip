@@ -19,6 +19,7 @@
 //   fe_stats_kernel   one lane per (utterance, dimension): the serial float sums of CMN() / MVN()
 //   fe_write_kernel   one lane per output element: normalisation and splicing -> out[T'][veclen * splice]
 #include "jamd_device.h"
+#include "frontend_host.h"
 #include "ss_file.h"
 #include <cmath>
 #include <cstdint>
@@ -881,7 +882,7 @@ int jamd_frontend_ss_write(const char *path, const float *noise, int n) {
 // The offsets go up through a pinned buffer that is rewritten only once the copy that read it is done.
 // blob = soff (int64 [nutt + 1]) followed by ntab int32 tables [nutt + 1].
 static int fe_put_offsets(jamd_frontend *f, hipStream_t st, const int64_t *sample_off, int nutt,
-                          std::initializer_list<const std::vector<int> *> tabs) {
+                          const std::vector<const std::vector<int> *> &tabs) {
   const size_t offb = sizeof(long long) * (nutt + 1) + tabs.size() * sizeof(int) * (nutt + 1);
   int rc;
   if ((rc = fe_reserve(&f->d_off, &f->off_cap, offb)) != JAMD_OK) return rc;
@@ -1104,3 +1105,30 @@ int jamd_frontend_run_host(jamd_frontend *f, const int16_t *samples, const int64
 }
 
 }  // extern "C"
+
+// ---- what csrc/frontend_live.hip takes from this unit (frontend_host.h)
+void fe_info(const jamd_frontend *f, FeInfo *out) {
+  out->eng = f->eng; out->d = f->d; out->ss_mode = f->ss_mode; out->fftN = f->tb.fftN;
+}
+
+int fe_base_frames(jamd_frontend *f, hipStream_t st, const int16_t *dev_samples, const int64_t *sample_off, int nutt,
+                   const std::vector<const std::vector<int> *> &tabs, const float **d_stat, const int **d_tabs) {
+  const int T = (*tabs[0])[nutt];
+  int rc;
+  if ((rc = fe_reserve(&f->d_stat, &f->stat_cap, (size_t)(T > 0 ? T : 1) * f->d.baselen)) != JAMD_OK) return rc;
+  if ((rc = fe_put_offsets(f, st, sample_off, nutt, tabs)) != JAMD_OK) return rc;
+  const long long *d_soff = (const long long *)f->d_off;
+  const int *d_foff = (const int *)(d_soff + nutt + 1);
+  *d_stat = f->d_stat; *d_tabs = d_foff;
+  if (T < 1) return JAMD_OK;
+  FeParams p = f->p;
+  p.nutt = nutt;
+  if (f->ss_mode == JAMD_SS_OFF)
+    hipLaunchKernelGGL(fe_frame_kernel<false>, dim3((T + f->fpb - 1) / f->fpb), dim3(64 * f->fpb), f->lds, st, p,
+                       dev_samples, d_soff, d_foff, T, f->d_stat, (const float *)nullptr, 0, 0.0f, 0.0f);
+  else
+    hipLaunchKernelGGL(fe_frame_kernel<true>, dim3((T + f->fpb - 1) / f->fpb), dim3(64 * f->fpb), f->lds, st, p,
+                       dev_samples, d_soff, d_foff, T, f->d_stat, (const float *)f->d_ssload, 0, f->ss_alpha, f->ss_floor);
+  JAMD_HIP(hipGetLastError());
+  return JAMD_OK;
+}

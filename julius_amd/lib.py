@@ -66,6 +66,13 @@ class FrontendSS(C.Structure):
                 ("noise", C.c_void_p), ("noise_len", C.c_int)]
 
 
+class FrontendLiveDesc(C.Structure):
+    """jamd_frontend_live_desc (include/julius_amd.h): -cmnstatic / -cmnmapweight / -cmnload of the live front end."""
+    _fields_ = [("map_cmn", C.c_int), ("map_weight", C.c_float), ("cmean_init", C.c_void_p), ("cvar_init", C.c_void_p)]
+
+
+LIVE_CMEAN_SET, LIVE_LOADED = 1, 2
+
 _lib = None
 
 
@@ -187,6 +194,17 @@ def load():
         "jamd_frontend_noise_host": (ci, [vp, vp, vp, ci, C.c_int64, vp]),
         "jamd_frontend_ss_read": (ci, [C.c_char_p, vp, ci]),
         "jamd_frontend_ss_write": (ci, [C.c_char_p, vp, ci]),
+        "jamd_frontend_live_default": (ci, [P(FrontendLiveDesc)]),
+        "jamd_frontend_live_create": (ci, [vp, P(FrontendLiveDesc), ci, P(vp)]),
+        "jamd_frontend_live_destroy": (None, [vp]),
+        "jamd_frontend_live_frames": (ci, [P(FrontendDesc), C.c_int64]),
+        "jamd_frontend_live_run_dev": (ci, [vp, vp, vp, vp, vp, vp]),
+        "jamd_frontend_live_run_host": (ci, [vp, vp, vp, vp, vp]),
+        "jamd_frontend_live_commit": (ci, [vp, vp, vp]),
+        "jamd_frontend_live_state_get": (ci, [vp, ci, vp, vp, vp, vp]),
+        "jamd_frontend_live_state_set": (ci, [vp, ci, vp, vp]),
+        "jamd_frontend_cmn_read": (ci, [C.c_char_p, ci, ci, ci, vp, vp]),
+        "jamd_frontend_cmn_write": (ci, [C.c_char_p, ci, vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -928,6 +946,106 @@ class Frontend:
     def close(self):
         if getattr(self, "h", None):
             load().jamd_frontend_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def cmn_read(path, veclen: int, mfcc_dim: int, want_var: bool = False):
+    """A -cmnload file (ASCII <CEPSNORM> or the old binary form) -> (mean [veclen], variance [veclen] or None), as
+    CMN_load_from_file() reads it; mfcc_dim counts the cepstra plus c0.  Raises where the reference refuses the file."""
+    cm, cv = np.zeros(veclen, np.float32), np.zeros(veclen, np.float32)
+    r = load().jamd_frontend_cmn_read(str(path).encode(), int(veclen), int(mfcc_dim), 1 if want_var else 0,
+                                      cm.ctypes.data, cv.ctypes.data)
+    if r < 0:
+        raise JamdError(f"jamd_frontend_cmn_read failed ({r}): {load().jamd_last_error().decode()}")
+    return cm, (cv if r == 1 else None)
+
+
+def cmn_write(path, cmean, cvar=None):
+    """CMN_save_to_file(): the ASCII form, with a <VARIANCE> block when cvar is given."""
+    cm = _f32(cmean).ravel()
+    cv = _f32(cvar).ravel() if cvar is not None else None
+    assert cv is None or len(cv) == len(cm)
+    _check(load().jamd_frontend_cmn_write(str(path).encode(), len(cm), cm.ctypes.data,
+                                          cv.ctypes.data if cv is not None else None), "jamd_frontend_cmn_write")
+
+
+class LiveFrontend:
+    """Live-input front end (jamd_frontend_live) over a created Frontend: one whole segment per channel and call, the
+    vectors of RealTimeMFCC() and the flush loop of RealTimeParam() (libjulius/src/realtime-1stpass.c), with the
+    MAP-CMN / energy state of every channel kept on the device between calls."""
+
+    def __init__(self, fe: Frontend, nchan: int, map_cmn: bool = True, map_weight: float = 100.0, cmean=None, cvar=None):
+        self.fe, self.nchan = fe, int(nchan)      # (keeps the parent alive)
+        self.veclen = fe.veclen
+        self.base_veclen = fe.desc.veclen
+        cm = _f32(cmean) if cmean is not None else None
+        cv = _f32(cvar) if cvar is not None else None
+        d = FrontendLiveDesc(1 if map_cmn else 0, float(map_weight), cm.ctypes.data if cm is not None else None,
+                             cv.ctypes.data if cv is not None else None)
+        h = C.c_void_p()
+        _check(load().jamd_frontend_live_create(fe.h, C.byref(d), self.nchan, C.byref(h)), "jamd_frontend_live_create")
+        self.h = h
+
+    def frames(self, nsamples: int) -> int:
+        return load().jamd_frontend_live_frames(C.byref(self.fe.desc), int(nsamples))
+
+    def run_host(self, segs):
+        """One int16 array per channel (empty = idle) -> (rows [sum T][veclen * splice], frame_off [nchan + 1])."""
+        assert len(segs) == self.nchan
+        samples, off = Frontend._pack(segs)
+        if len(samples) == 0:
+            samples = np.zeros(1, np.int16)
+        T = sum(self.frames(off[c + 1] - off[c]) for c in range(self.nchan))
+        out = np.zeros((T, self.veclen), np.float32)
+        foff = np.zeros(self.nchan + 1, np.int32)
+        buf = out if T else np.zeros((1, self.veclen), np.float32)
+        _check(load().jamd_frontend_live_run_host(self.h, samples.ctypes.data, off.ctypes.data, buf.ctypes.data,
+                                                  foff.ctypes.data), "jamd_frontend_live_run_host")
+        return out, foff
+
+    def run_dev(self, dev_samples: int, sample_off, dev_out: int, stream: int = 0):
+        """Device samples and rows; sample_off host int64 [nchan + 1].  Returns frame_off [nchan + 1]."""
+        off = np.ascontiguousarray(sample_off, dtype=np.int64)
+        assert len(off) == self.nchan + 1
+        foff = np.zeros(len(off), np.int32)
+        _check(load().jamd_frontend_live_run_dev(self.h, dev_samples, off.ctypes.data, dev_out, foff.ctypes.data,
+                                                 stream or None), "jamd_frontend_live_run_dev")
+        return foff
+
+    def commit(self, update=None, stream: int = 0):
+        """CMN_realtime_update() for the channels whose entry of `update` is true (None: every channel)."""
+        m = None
+        if update is not None:
+            m = np.ascontiguousarray(np.asarray(update).astype(bool), dtype=np.uint8)
+            assert len(m) == self.nchan
+        _check(load().jamd_frontend_live_commit(self.h, m.ctypes.data if m is not None else None, stream or None),
+               "jamd_frontend_live_commit")
+
+    def state(self, chan: int):
+        """(cmean_init [veclen], cvar_init [veclen], energy maximum, flags) of one channel, after everything queued."""
+        cm, cv = np.zeros(self.base_veclen, np.float32), np.zeros(self.base_veclen, np.float32)
+        em, fl = C.c_float(0), C.c_int(0)
+        _check(load().jamd_frontend_live_state_get(self.h, int(chan), cm.ctypes.data, cv.ctypes.data,
+                                                   C.addressof(em), C.addressof(fl)), "jamd_frontend_live_state_get")
+        return cm, cv, np.float32(em.value), fl.value
+
+    def set_state(self, chan: int, cmean, cvar=None):
+        cm = _f32(cmean).ravel()
+        cv = _f32(cvar).ravel() if cvar is not None else None
+        assert len(cm) == self.base_veclen and (cv is None or len(cv) == self.base_veclen)
+        _check(load().jamd_frontend_live_state_set(self.h, int(chan), cm.ctypes.data,
+                                                   cv.ctypes.data if cv is not None else None),
+               "jamd_frontend_live_state_set")
+
+    def close(self):
+        if getattr(self, "h", None):
+            load().jamd_frontend_live_destroy(self.h)
             self.h = None
 
     def __del__(self):
