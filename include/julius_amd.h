@@ -788,10 +788,13 @@ int  jamd_frontend_ss_write(const char *path, const float *noise, int n);
  * carries from one utterance to the next (ENERGYWork.max, CMNWork) is kept per channel on the device.
  * Which julius option is which call: INTEGRATION.md.
  *
- * NOT SERVED: chunked input inside a segment (one call = one whole segment per channel); _N together with _A
- * (refused by _create: the reference's two loops disagree on it, realtime-1stpass.c:1233-1241 against :583-587);
- * JAMD_SS_CALC on the parent (refused by _run: a live segment has no head known in advance); frameshift beyond the
- * window; gzipped -cmnload files. */
+ * A segment goes in whole (jamd_frontend_live_run_*) or in chunks cut anywhere (jamd_frontend_live_push_*): the
+ * reference is frame-synchronous, so both deliver the same rows and leave the same state.
+ *
+ * NOT SERVED: _N together with _A (refused by _create: the reference's two loops disagree on it,
+ * realtime-1stpass.c:1233-1241 against :583-587); JAMD_SS_CALC on the parent (refused by _run / _push: a live segment
+ * has no head known in advance); frameshift beyond the window; -48, -lv, -zmean and zero-sample stripping on live
+ * input; gzipped -cmnload files. */
 typedef struct {
   int   map_cmn;                 /* 1 = MAP-CMN, 0 = -cmnstatic (CMNWork.do_map)                          */
   float map_weight;              /* -cmnmapweight                                                         */
@@ -824,6 +827,37 @@ int  jamd_frontend_live_run_dev (jamd_frontend_live *l, const int16_t *dev_sampl
                                  float *dev_out, int *frame_off, void *stream);
 int  jamd_frontend_live_run_host(jamd_frontend_live *l, const int16_t *samples, const int64_t *sample_off, float *out,
                                  int *frame_off);
+/* A segment in chunks.  Channel c appends samples [sample_off[c], sample_off[c+1]) (host offsets [nchan + 1]) to its
+ * open segment; its first push after creation or after a segment ended opens one (reset_mfcc() +
+ * CMN_realtime_prepare() + energy_max_prepare()).  A non-zero byte of `final` ([nchan], host; NULL = none) ends the
+ * channel's segment behind this chunk: the flush loop of RealTimeParam() runs, the segment's energy maximum becomes the
+ * next one's, and now.mfcc_sum / mfcc_var / framenum are where jamd_frontend_live_commit() reads them.  The rows the
+ * call completes go back to back into dev_out, their host offsets into frame_off (may be NULL); how many a push
+ * yields: jamd_frontend_live_push_frames().  However a segment is cut, its pushes deliver, concatenated, the rows one
+ * jamd_frontend_live_run_*() over the concatenated samples delivers, and leave the same state.  A channel with no
+ * samples and a zero byte is untouched; with no samples and a non-zero byte its open segment ends (without one:
+ * nothing happens).  dev_samples may be NULL when no channel has samples, dev_out when no row is due.
+ * Per channel the device keeps the samples behind the last whole window, the last 2 * (delWin + accWin) base vectors,
+ * the running energy maximum, the CMN chains and the last splice - 1 vectors.  The call is queued on `stream` and
+ * allocates only when a buffer has to grow; like _run_dev it waits for the previous call's offset upload alone.
+ * While a channel's segment is open, _run_* (any channel open), _commit with a non-zero byte for it and _state_set on
+ * it return JAMD_ESTATE.  Whole segments and chunked ones may alternate on one object. */
+int  jamd_frontend_live_push_dev (jamd_frontend_live *l, const int16_t *dev_samples, const int64_t *sample_off,
+                                  const unsigned char *final, float *dev_out, int *frame_off, void *stream);
+int  jamd_frontend_live_push_host(jamd_frontend_live *l, const int16_t *samples, const int64_t *sample_off,
+                                  const unsigned char *final, float *out, int *frame_off);
+/* Host only.  Rows a push of `chunk` samples yields on a segment that has taken samples_before.  With
+ * L = (delta ? delWin : 0) + (acc ? accWin : 0) and Tb(n) the base frames of n samples, max(0, Tb - L) vectors have
+ * left the main loop before the end, and from the splice-th on each completes a row:
+ * max(0, max(0, Tb - L) - (splice - 1)) rows so far.  final != 0: what is left of jamd_frontend_live_frames() of
+ * all the samples. */
+int  jamd_frontend_live_push_frames(const jamd_frontend_desc *d, int64_t samples_before, int64_t chunk, int final);
+/* With cvn and splice 1 the reference re-estimates now.mfcc_var at the end of a segment from every stored row
+ * (wav2mfcc-pipe.c:418-434), so the object keeps the rows of each open segment: at most max_rows per channel
+ * (default 3000, half a minute at 10 ms; the buffer grows on demand up to it).  A push that would pass it returns
+ * JAMD_EINVAL before anything is launched, the state unchanged.  Other kinds keep no rows.  JAMD_ESTATE while a
+ * segment is open. */
+int  jamd_frontend_live_stream_cap(jamd_frontend_live *l, int max_rows);
 /* CMN_realtime_update(wrk, param) (wav2mfcc-pipe.c:407-479) for the channels whose byte of `update` ([nchan], host) is
  * non-zero; NULL = every channel.  -cmnnoupdate: never call it; an input that was rejected
  * (realtime-1stpass.c:1416-1442): a zero byte.  Queued on `stream` behind the run it belongs to.  It is that call

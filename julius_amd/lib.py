@@ -200,6 +200,10 @@ def load():
         "jamd_frontend_live_frames": (ci, [P(FrontendDesc), C.c_int64]),
         "jamd_frontend_live_run_dev": (ci, [vp, vp, vp, vp, vp, vp]),
         "jamd_frontend_live_run_host": (ci, [vp, vp, vp, vp, vp]),
+        "jamd_frontend_live_push_dev": (ci, [vp, vp, vp, vp, vp, vp, vp]),
+        "jamd_frontend_live_push_host": (ci, [vp, vp, vp, vp, vp, vp]),
+        "jamd_frontend_live_push_frames": (ci, [P(FrontendDesc), C.c_int64, C.c_int64, ci]),
+        "jamd_frontend_live_stream_cap": (ci, [vp, ci]),
         "jamd_frontend_live_commit": (ci, [vp, vp, vp]),
         "jamd_frontend_live_state_get": (ci, [vp, ci, vp, vp, vp, vp]),
         "jamd_frontend_live_state_set": (ci, [vp, ci, vp, vp]),
@@ -976,9 +980,10 @@ def cmn_write(path, cmean, cvar=None):
 
 
 class LiveFrontend:
-    """Live-input front end (jamd_frontend_live) over a created Frontend: one whole segment per channel and call, the
-    vectors of RealTimeMFCC() and the flush loop of RealTimeParam() (libjulius/src/realtime-1stpass.c), with the
-    MAP-CMN / energy state of every channel kept on the device between calls."""
+    """Live-input front end (jamd_frontend_live) over a created Frontend: per channel and call one whole segment (run_*)
+    or the next chunk of an open one (push_*), the vectors of RealTimeMFCC() and the flush loop of RealTimeParam()
+    (libjulius/src/realtime-1stpass.c), with the MAP-CMN / energy state of every channel kept on the device between
+    calls."""
 
     def __init__(self, fe: Frontend, nchan: int, map_cmn: bool = True, map_weight: float = 100.0, cmean=None, cvar=None):
         self.fe, self.nchan = fe, int(nchan)      # (keeps the parent alive)
@@ -1016,6 +1021,50 @@ class LiveFrontend:
         foff = np.zeros(len(off), np.int32)
         _check(load().jamd_frontend_live_run_dev(self.h, dev_samples, off.ctypes.data, dev_out, foff.ctypes.data,
                                                  stream or None), "jamd_frontend_live_run_dev")
+        return foff
+
+    def push_frames(self, samples_before: int, chunk: int, final: bool = False) -> int:
+        """Rows a push of `chunk` samples yields on a segment that has taken samples_before."""
+        return load().jamd_frontend_live_push_frames(C.byref(self.fe.desc), int(samples_before), int(chunk),
+                                                     1 if final else 0)
+
+    def stream_cap(self, max_rows: int):
+        """Rows of an open segment kept per channel for the variance re-estimation (cvn with splice 1)."""
+        _check(load().jamd_frontend_live_stream_cap(self.h, int(max_rows)), "jamd_frontend_live_stream_cap")
+
+    def _final(self, final):
+        if final is None:
+            return None
+        m = np.ascontiguousarray(np.asarray(final).astype(bool), dtype=np.uint8)
+        assert len(m) == self.nchan
+        return m
+
+    def push_host(self, chunks, final=None):
+        """The next int16 chunk of every channel's open segment (empty = none; the first opens one); `final` marks the
+        channels whose segment ends behind it -> (rows completed [sum T][veclen * splice], frame_off [nchan + 1])."""
+        assert len(chunks) == self.nchan
+        samples, off = Frontend._pack(chunks)
+        if len(samples) == 0:
+            samples = np.zeros(1, np.int16)
+        m = self._final(final)
+        d = self.fe.desc                         # a push completes at most the frames its samples and the delays hold
+        max_rows = int(off[-1]) // d.frameshift + self.nchan * (d.delWin + d.accWin + 2)
+        buf = np.zeros((max_rows, self.veclen), np.float32)
+        foff = np.zeros(self.nchan + 1, np.int32)
+        _check(load().jamd_frontend_live_push_host(self.h, samples.ctypes.data, off.ctypes.data,
+                                                   m.ctypes.data if m is not None else None, buf.ctypes.data,
+                                                   foff.ctypes.data), "jamd_frontend_live_push_host")
+        return buf[:int(foff[-1])].copy(), foff
+
+    def push_dev(self, dev_samples: int, sample_off, dev_out: int, final=None, stream: int = 0):
+        """Device samples and rows; sample_off host int64 [nchan + 1].  Returns frame_off [nchan + 1]."""
+        off = np.ascontiguousarray(sample_off, dtype=np.int64)
+        assert len(off) == self.nchan + 1
+        m = self._final(final)
+        foff = np.zeros(len(off), np.int32)
+        _check(load().jamd_frontend_live_push_dev(self.h, dev_samples or None, off.ctypes.data,
+                                                  m.ctypes.data if m is not None else None, dev_out or None,
+                                                  foff.ctypes.data, stream or None), "jamd_frontend_live_push_dev")
         return foff
 
     def commit(self, update=None, stream: int = 0):
