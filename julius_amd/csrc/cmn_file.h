@@ -1,6 +1,6 @@
 // cmn_file.h -- the cepstral mean / variance file of `-cmnload` / `-cmnsave` (read by CMN_load_from_file(), written by
 // CMN_save_to_file(), libsent/src/wav2mfcc/wav2mfcc-pipe.c:514-696).  Plain C++ without device code, like ss_file.h:
-// csrc/frontend_live.hip wraps the two functions in the C ABI (jamd_frontend_cmn_read / _write), and
+// csrc/frontend_live_api.hip wraps the two functions in the C ABI (jamd_frontend_cmn_read / _write), and
 // tests/cmn_file_check.cpp compiles them alone under the host sanitizers.  Two forms are read:
 //   - the ASCII form (Julius >= 4.3): "<CEPSNORM> <>", "<MEAN> n" with n == veclen or n == mfcc_dim values (the rest of
 //     the mean is zero), and an optional "<VARIANCE> veclen" block; tokens are split at "<> \t\r\n" as there (quoting,

@@ -1,4 +1,4 @@
-// jamd_device.h -- device-side helpers shared by the scoring and first-pass kernels (the Gaussian kernels' own: gmm_dev.h).
+// jamd_device.h -- device-side helpers shared by the scoring, first-pass and front-end kernels (the Gaussian kernels' own: gmm_dev.h).
 #pragma once
 #include "jamd_internal.h"
 
@@ -14,6 +14,13 @@ __device__ __forceinline__ void wave_release() {
 __device__ __forceinline__ void wave_sync() {
   wave_release();
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// The u with off[u] <= g < off[u + 1] of an ascending offset table off[0 .. n] (the front ends' frames -> utterance).
+__device__ __forceinline__ int find_span(const int *off, int n, int g) {
+  int lo = 0, hi = n;
+  while (hi - lo > 1) { int mid = (lo + hi) >> 1; if (off[mid] <= g) lo = mid; else hi = mid; }
+  return lo;
 }
 
 // One step of addlog_array() (libsent/src/phmm/addlog.c:108-121): y is the

@@ -12,9 +12,10 @@
 // addlog.c:28-30
 #define JAMD_TBLSIZE 500000
 #define JAMD_TMAG 33333.3333
-// stddefs.h:176 / :111 (double constants in the reference)
+// stddefs.h:176 / :111 / :109 (double constants in the reference)
 #define JAMD_LOG_ADDMIN (-13.815510558)
 #define JAMD_INV_LOG_TEN (.434294482)
+#define JAMD_LOG_TEN 2.30258509
 // calc_dnn.c:344-347
 #define JAMD_LOGISTIC_FACTOR 20000
 #define JAMD_LOGISTIC_MAX (16 * JAMD_LOGISTIC_FACTOR)

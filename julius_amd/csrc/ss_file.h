@@ -1,6 +1,6 @@
 // ss_file.h -- the noise-spectrum file of `mkss` / `-ssload` (written by mkss/mkss.c:219-233, read by
 // new_SS_load_from_file(), libsent/src/wav2mfcc/ss.c:65-96): a big-endian int32 count, then that many
-// big-endian float32.  Plain C++ without device code: csrc/frontend.hip wraps the two functions in the C ABI
+// big-endian float32.  Plain C++ without device code: csrc/frontend_api.hip wraps the two functions in the C ABI
 // (jamd_frontend_ss_read / _write), and tests/ss_file_check.cpp compiles them alone under the host sanitizers.
 // The reader takes nothing in the file on trust: the count sizes no allocation, and the values are copied in
 // fixed pieces up to the caller's capacity.

@@ -1,4 +1,4 @@
-"""Device audio front end (csrc/frontend.hip) where its kernels change path, bit for bit against the
+"""Device audio front end (csrc/frontend.hip behind csrc/frontend_api.hip) where its kernels change path, bit for bit against the
 compiled reference's Wav2MFCC() plus splicing (tests/test_frontend_gpu.py holds it at speech defaults):
 windows from 16 to 4096 samples with and without zero padding, more than 64 channels / coefficients,
 calls smaller than one workgroup of the frame kernel, delta windows longer than the utterance,

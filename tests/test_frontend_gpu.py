@@ -1,4 +1,4 @@
-"""Device audio front end (csrc/frontend.hip) against the compiled reference's Wav2MFCC()
+"""Device audio front end (csrc/frontend.hip behind csrc/frontend_api.hip) against the compiled reference's Wav2MFCC()
 (libsent/src/wav2mfcc/wav2mfcc-buffer.c) plus libjulius' splicing, bit for bit.
 
 Where the reference produces NaN (an all-zero utterance under ENORMALISE: -inf - -inf), the device

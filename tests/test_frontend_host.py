@@ -1,6 +1,8 @@
-"""Host half of the audio front end (csrc/frontend.hip) against the compiled reference: the descriptor
-defaults, the HTK config parser, every table WMP_work_new() builds, and the frame count.  No GPU."""
+"""Host half of the audio front end (csrc/frontend_tables.h behind csrc/frontend_api.hip) against the compiled
+reference: the descriptor defaults, the HTK config parser, every table WMP_work_new() builds, and the frame count; and
+that header as a stand-alone program under the host sanitizers.  No GPU."""
 import ctypes as C
+import subprocess
 
 import numpy as np
 import pytest
@@ -152,6 +154,24 @@ def test_frames(n, splice):
     want = (n - 400) // 160 + 1 - (splice - 1) if n >= 400 else 1 - splice
     got = lib.load().jamd_frontend_frames(C.byref(d), n)
     assert got == want if want > 0 else got <= 0
+
+
+def test_tables_parser_and_counts_under_sanitizers(tmp_path):
+    """tests/frontend_tables_check.cpp (its own main over csrc/frontend_tables.h, which includes no HIP header) built
+    with -fsanitize=address,undefined, the runtimes linked statically: HTK configs with CRLF ends, missing values and
+    over-long lines, refused keys, tables for windows of 2 to 4096 samples, band limits, VTLN accepted and refused, one
+    channel, and the live counts of every sample count cut at every point: every case as expected and no report."""
+    exe = tmp_path / "frontend_tables_check"
+    root = lib._PKG.parent
+    subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined",
+                    "-fno-sanitize-recover=all", "-static-libasan", "-static-libubsan", "-I", str(lib._PKG / "csrc"),
+                    "-I", str(root / "include"), str(root / "tests" / "frontend_tables_check.cpp"), "-o", str(exe)],
+                   check=True)
+    work = tmp_path / "files"
+    work.mkdir()
+    r = subprocess.run([str(exe), str(work)], capture_output=True, text=True)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert "FAILED" not in r.stdout and r.stdout.count("ok:") >= 40 and "Sanitizer" not in r.stderr
 
 
 def test_param_kind_codes():

@@ -1,4 +1,4 @@
-"""Spectral subtraction of the device front end (jamd_frontend_set_ss, jamd_frontend_noise_*; csrc/frontend.hip)
+"""Spectral subtraction of the device front end (jamd_frontend_set_ss, jamd_frontend_noise_*; csrc/frontend.hip behind csrc/frontend_api.hip)
 against the compiled reference, bit for bit (NaN as NaN): the noise spectrum against new_SS_calculate(), the features
 of -sscalc / -ssload against Wav2MFCC() with that spectrum on its work area plus libjulius' splicing.
 

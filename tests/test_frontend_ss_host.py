@@ -1,4 +1,4 @@
-"""Host half of the spectral subtraction (csrc/frontend.hip, csrc/ss_file.h): the mkss / -ssload file format against
+"""Host half of the spectral subtraction (csrc/frontend_api.hip, csrc/ss_file.h): the mkss / -ssload file format against
 the reference's new_SS_load_from_file(), the defaults of jamd_frontend_ss_default() against the reference's, and the
 file reader and writer as a stand-alone program under the host sanitizers.  No GPU."""
 import ctypes as C

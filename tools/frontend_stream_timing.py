@@ -14,7 +14,7 @@ Per channel count:
   host_us_per_push   host clock around the push calls of a segment alone (enqueue), over 57
 For 512 channels the segment as pushes, as one run_dev of this library and -- with --parent-lib, the library built from
 the parent commit, loaded beside this one -- as one run_dev of the parent alternate in one process.
-launches_per_push is what the code enqueues for a push that completes frames (csrc/frontend_live.hip); a kernel trace
+launches_per_push is what the code enqueues for a push that completes frames (csrc/frontend_live_api.hip); a kernel trace
 of this tool counts the same."""
 import argparse
 import ctypes as C
