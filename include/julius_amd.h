@@ -793,8 +793,8 @@ int  jamd_frontend_ss_write(const char *path, const float *noise, int n);
  *
  * NOT SERVED: _N together with _A (refused by _create: the reference's two loops disagree on it,
  * realtime-1stpass.c:1233-1241 against :583-587); JAMD_SS_CALC on the parent (refused by _run / _push: a live segment
- * has no head known in advance); frameshift beyond the window; -48, -lv, -zmean and zero-sample stripping on live
- * input; gzipped -cmnload files. */
+ * has no head known in advance); frameshift beyond the window; silence cutting (-cutsilence, -lv); gzipped -cmnload
+ * files.  -48, -lvscale, -zmean and zero-sample stripping: jamd_adin_*, in front of this object. */
 typedef struct {
   int   map_cmn;                 /* 1 = MAP-CMN, 0 = -cmnstatic (CMNWork.do_map)                          */
   float map_weight;              /* -cmnmapweight                                                         */
@@ -877,6 +877,65 @@ int  jamd_frontend_live_state_set(jamd_frontend_live *l, int chan, const float *
  * cvar == NULL writes no variance. */
 int  jamd_frontend_cmn_read (const char *path, int veclen, int mfcc_dim, int want_var, float *cmean, float *cvar);
 int  jamd_frontend_cmn_write(const char *path, int veclen, const float *cmean, const float *cvar);
+
+/* ---- audio conditioning in front of the two front ends: -48, -lvscale, zero stripping, -zmean -------------
+ * What adin_cut() does to the samples of one ad_read() before anything looks at them (libjulius/src/adin-cut.c:470-545),
+ * bit-identical and in its order: ds48to16() (three double FIR stages 48 -> 64 -> 32 -> 16 kHz), the level scaling
+ * (SP16)((float)s * coef), strip_zero() (runs of 16 or more samples that are 0 or -32767 are dropped) and sub_zmean()
+ * (the mean of the first 48000 samples, estimated chunk by chunk).  strip_zero() and sub_zmean() act per read, so their
+ * result depends on how the input was cut: one push is one ad_read() per channel.  For file input the reference's first
+ * read asks for 320000 samples (960000 under -48): a file shorter than 20 s is one chunk.  The output is what
+ * jamd_frontend_run_dev() / jamd_frontend_live_push_dev() take as dev_samples, the offsets their sample_off: samples
+ * never visit the host.  The down-sampling state (filter history, pending samples, the spent delay) and the DC state
+ * (zlen, zmean) are kept per channel on the device.  The reference resets the second at every stream start
+ * (zmean_reset(), adin-cut.c:1416,1444) and the first never (the DS_BUFFER is made once, m_adin.c:216): the program
+ * carries filter state from one file into the next, hence the two bits of jamd_adin_reset().  ds48to16_new() leaves the
+ * filter history uninitialised; here the samples before the stream start are 0.0.
+ * NOT SERVED: silence cutting (-cutsilence, -lv, zero-cross counting). */
+typedef struct {
+  int   down48;                  /* -48: the input is 48 kHz                                              */
+  const double *fir_3to4;        /* the caller's lpfcoef_3to4[] (n_3to4 entries) and lpfcoef_2to1[]: from */
+  int   n_3to4;                  /* libsent, or a file through jamd_adin_fir_read(); 1 ... 513 entries    */
+  const double *fir_2to1;        /* each, needed with down48, copied by _create                           */
+  int   n_2to1;
+  float level_coef;              /* -lvscale; applied when != 1.0; 32768 * |coef| < 2^31                  */
+  int   strip_zero;              /* default 1 (default.c:92); -nostrip: 0                                 */
+  int   zmean;                   /* -zmean                                                                */
+} jamd_adin_desc;
+typedef struct jamd_adin jamd_adin;
+#define JAMD_ADIN_DS    1        /* jamd_adin_reset(): the down-sampling state, as ds48to16_new() leaves it */
+#define JAMD_ADIN_ZMEAN 2        /*                    zmean_reset()                                        */
+
+int  jamd_adin_default(jamd_adin_desc *d);                   /* 0, NULL / 0, NULL / 0, 1.0, 1, 0 */
+/* host only: the text format of the reference's load_filter(): one atof() per line, 513 entries at the most.  Returns
+ * the number of entries; JAMD_EINVAL for a file that cannot be read, holds none, or holds more than `cap`. */
+int  jamd_adin_fir_read(const char *path, double *out, int cap);
+/* nchan channels, each as ds48to16_new() + zmean_reset() leave it */
+int  jamd_adin_create(jamd_engine *e, const jamd_adin_desc *d, int nchan, jamd_adin **out);
+void jamd_adin_destroy(jamd_adin *a);
+/* The channels with a non-zero byte of mask ([nchan], host; NULL = all) go back to the start: `what` is
+ * JAMD_ADIN_DS | JAMD_ADIN_ZMEAN or one of them.  Queued on `stream`. */
+int  jamd_adin_reset(jamd_adin *a, const unsigned char *mask, int what, void *stream);
+/* host only: 16 kHz samples that a push of `chunk` 48 kHz samples completes on a channel that has taken
+ * samples_before since its last JAMD_ADIN_DS reset.  Each stage consumes whole blocks of 256 of its input and drops its
+ * first hdn_len / (2 * decrate) outputs, so the first 767 samples of a stream yield nothing.  Needs n_3to4 / n_2to1 of
+ * the descriptor only.  Without down48: chunk. */
+int64_t jamd_adin_ds_count(const jamd_adin_desc *d, int64_t samples_before, int64_t chunk);
+/* host only: an upper bound of what such a push writes (zero stripping can only shorten it), for sizing dev_out */
+int64_t jamd_adin_push_cap(const jamd_adin_desc *d, int64_t samples_before, int64_t chunk);
+/* One chunk per channel: channel c's is [in_off[c], in_off[c+1]) of dev_in (host offsets [nchan + 1]).  The conditioned
+ * samples go back to back into dev_out (room: the sum of jamd_adin_push_cap()), their host offsets [nchan + 1] into
+ * out_off.  A channel with an empty chunk is idle: its state is untouched and sub_zmean() is not called; a chunk that
+ * stripping empties still is one (with zlen 0 the reference's mean becomes 0 / 0 and every later sample 0; so here).
+ * With strip_zero the counts are data: the call returns after they have arrived, which costs one wait on `stream`.
+ * Without it they are closed-form and the call only enqueues.  One stream per object, as for jamd_frontend_run_dev(). */
+int  jamd_adin_push_dev (jamd_adin *a, const int16_t *dev_in, const int64_t *in_off, int16_t *dev_out, int64_t *out_off,
+                         void *stream);
+/* The same from and to host memory, on the engine's stream; `out` has room for the sum of jamd_adin_push_cap(). */
+int  jamd_adin_push_host(jamd_adin *a, const int16_t *samples, const int64_t *in_off, int16_t *out, int64_t *out_off);
+/* One channel after everything queued so far (waits for the device): sub_zmean()'s zlen and zmean, and per FIR stage the
+ * inputs arrived and the outputs handed on since the last JAMD_ADIN_DS reset ([3] each).  Any pointer may be NULL. */
+int  jamd_adin_state_get(jamd_adin *a, int chan, int *zlen, float *zmean, int64_t *arrived, int64_t *emitted);
 
 #ifdef __cplusplus
 }

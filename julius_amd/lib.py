@@ -73,6 +73,15 @@ class FrontendLiveDesc(C.Structure):
 
 LIVE_CMEAN_SET, LIVE_LOADED = 1, 2
 
+
+class AdinDesc(C.Structure):
+    """jamd_adin_desc (include/julius_amd.h): -48 with the caller's two FIR tables, -lvscale, -nostrip, -zmean."""
+    _fields_ = [("down48", C.c_int), ("fir_3to4", C.c_void_p), ("n_3to4", C.c_int), ("fir_2to1", C.c_void_p),
+                ("n_2to1", C.c_int), ("level_coef", C.c_float), ("strip_zero", C.c_int), ("zmean", C.c_int)]
+
+
+ADIN_DS, ADIN_ZMEAN = 1, 2
+
 _lib = None
 
 
@@ -209,6 +218,16 @@ def load():
         "jamd_frontend_live_state_set": (ci, [vp, ci, vp, vp]),
         "jamd_frontend_cmn_read": (ci, [C.c_char_p, ci, ci, ci, vp, vp]),
         "jamd_frontend_cmn_write": (ci, [C.c_char_p, ci, vp, vp]),
+        "jamd_adin_default": (ci, [P(AdinDesc)]),
+        "jamd_adin_fir_read": (ci, [C.c_char_p, vp, ci]),
+        "jamd_adin_create": (ci, [vp, P(AdinDesc), ci, P(vp)]),
+        "jamd_adin_destroy": (None, [vp]),
+        "jamd_adin_reset": (ci, [vp, vp, ci, vp]),
+        "jamd_adin_ds_count": (C.c_int64, [P(AdinDesc), C.c_int64, C.c_int64]),
+        "jamd_adin_push_cap": (C.c_int64, [P(AdinDesc), C.c_int64, C.c_int64]),
+        "jamd_adin_push_dev": (ci, [vp, vp, vp, vp, vp, vp]),
+        "jamd_adin_push_host": (ci, [vp, vp, vp, vp, vp]),
+        "jamd_adin_state_get": (ci, [vp, ci, vp, vp, vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -1095,6 +1114,107 @@ class LiveFrontend:
     def close(self):
         if getattr(self, "h", None):
             load().jamd_frontend_live_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def adin_fir_read(path, cap: int = 513) -> np.ndarray:
+    """A FIR coefficient file in the text format of the reference's load_filter() -> float64 [n]."""
+    out = np.zeros(int(cap), np.float64)
+    n = load().jamd_adin_fir_read(str(path).encode(), out.ctypes.data, int(cap))
+    if n < 0:
+        _check(n, "jamd_adin_fir_read")
+    return out[:n].copy()
+
+
+class Adin:
+    """Audio conditioning in front of the front ends (jamd_adin): per push and channel one ad_read() chunk through
+    ds48to16() (-48), the level scaling (-lvscale), strip_zero() and sub_zmean() (-zmean) of adin_cut()
+    (libjulius/src/adin-cut.c:470-545), with the filter and DC state of every channel kept on the device."""
+
+    def __init__(self, eng: Engine, nchan: int, desc: "AdinDesc | None" = None, **fields):
+        self.eng, self.nchan = eng, int(nchan)
+        self.desc = desc if desc is not None else self.desc_for(**fields)
+        h = C.c_void_p()
+        _check(load().jamd_adin_create(eng.h, C.byref(self.desc), self.nchan, C.byref(h)), "jamd_adin_create")
+        self.h = h
+
+    @staticmethod
+    def desc_for(fir_3to4=None, fir_2to1=None, down48=None, level_coef: float = 1.0, strip_zero: bool = True,
+                 zmean: bool = False) -> AdinDesc:
+        """jamd_adin_default(), then the fields given; down48 defaults to whether tables were passed."""
+        d = AdinDesc()
+        _check(load().jamd_adin_default(C.byref(d)), "jamd_adin_default")
+        d._keep = []                             # (the descriptor borrows the tables)
+        for name, t in (("3to4", fir_3to4), ("2to1", fir_2to1)):
+            if t is not None:
+                t = np.ascontiguousarray(t, dtype=np.float64)
+                d._keep.append(t)
+                setattr(d, "fir_" + name, t.ctypes.data)
+                setattr(d, "n_" + name, len(t))
+        d.down48 = int((fir_3to4 is not None and fir_2to1 is not None) if down48 is None else down48)
+        d.level_coef, d.strip_zero, d.zmean = float(level_coef), int(bool(strip_zero)), int(bool(zmean))
+        return d
+
+    def ds_count(self, samples_before: int, chunk: int) -> int:
+        """16 kHz samples a push of `chunk` 48 kHz samples completes behind samples_before (host only)."""
+        n = load().jamd_adin_ds_count(C.byref(self.desc), int(samples_before), int(chunk))
+        if n < 0:
+            _check(n, "jamd_adin_ds_count")
+        return n
+
+    def push_cap(self, samples_before: int, chunk: int) -> int:
+        n = load().jamd_adin_push_cap(C.byref(self.desc), int(samples_before), int(chunk))
+        if n < 0:
+            _check(n, "jamd_adin_push_cap")
+        return n
+
+    def reset(self, mask=None, what: int = ADIN_DS | ADIN_ZMEAN, stream: int = 0):
+        m = None
+        if mask is not None:
+            m = np.ascontiguousarray(np.asarray(mask).astype(bool), dtype=np.uint8)
+            assert len(m) == self.nchan
+        _check(load().jamd_adin_reset(self.h, m.ctypes.data if m is not None else None, int(what), stream or None),
+               "jamd_adin_reset")
+
+    def push_host(self, chunks):
+        """One int16 chunk per channel (empty = idle) -> (conditioned samples back to back, out_off int64 [nchan + 1])."""
+        assert len(chunks) == self.nchan
+        samples, off = Frontend._pack(chunks)
+        cap = sum(self.push_cap(int(self.state(c)[2][0]), len(chunks[c])) for c in range(self.nchan)) \
+            if self.desc.down48 else len(samples)
+        out = np.zeros(max(cap, 1), np.int16)
+        ooff = np.zeros(self.nchan + 1, np.int64)
+        _check(load().jamd_adin_push_host(self.h, samples.ctypes.data if len(samples) else None, off.ctypes.data,
+                                          out.ctypes.data, ooff.ctypes.data), "jamd_adin_push_host")
+        return out[:int(ooff[-1])].copy(), ooff
+
+    def push_dev(self, dev_in: int, in_off, dev_out: int, stream: int = 0):
+        """Device samples in and out; in_off host int64 [nchan + 1].  Returns out_off int64 [nchan + 1]: with dev_out
+        what Frontend.run_dev() / LiveFrontend.push_dev() take as dev_samples and sample_off."""
+        off = np.ascontiguousarray(in_off, dtype=np.int64)
+        assert len(off) == self.nchan + 1
+        ooff = np.zeros(self.nchan + 1, np.int64)
+        _check(load().jamd_adin_push_dev(self.h, dev_in or None, off.ctypes.data, dev_out or None, ooff.ctypes.data,
+                                         stream or None), "jamd_adin_push_dev")
+        return ooff
+
+    def state(self, chan: int):
+        """(zlen, zmean, arrived [3], emitted [3]) of one channel, after everything queued."""
+        zl, zm = C.c_int(0), C.c_float(0)
+        arr, emi = np.zeros(3, np.int64), np.zeros(3, np.int64)
+        _check(load().jamd_adin_state_get(self.h, int(chan), C.addressof(zl), C.addressof(zm), arr.ctypes.data,
+                                          emi.ctypes.data), "jamd_adin_state_get")
+        return zl.value, np.float32(zm.value), arr, emi
+
+    def close(self):
+        if getattr(self, "h", None):
+            load().jamd_adin_destroy(self.h)
             self.h = None
 
     def __del__(self):
