@@ -793,8 +793,9 @@ int  jamd_frontend_ss_write(const char *path, const float *noise, int n);
  *
  * NOT SERVED: _N together with _A (refused by _create: the reference's two loops disagree on it,
  * realtime-1stpass.c:1233-1241 against :583-587); JAMD_SS_CALC on the parent (refused by _run / _push: a live segment
- * has no head known in advance); frameshift beyond the window; silence cutting (-cutsilence, -lv); gzipped -cmnload
- * files.  -48, -lvscale, -zmean and zero-sample stripping: jamd_adin_*, in front of this object. */
+ * has no head known in advance); frameshift beyond the window; gzipped -cmnload files.  -48, -lvscale, -zmean and
+ * zero-sample stripping: jamd_adin_*; silence cutting (-cutsilence, -lv, -zc): jamd_adin_cut_*, whose rows are this
+ * object's pushes; both in front of this object. */
 typedef struct {
   int   map_cmn;                 /* 1 = MAP-CMN, 0 = -cmnstatic (CMNWork.do_map)                          */
   float map_weight;              /* -cmnmapweight                                                         */
@@ -891,7 +892,7 @@ int  jamd_frontend_cmn_write(const char *path, int veclen, const float *cmean, c
  * (zmean_reset(), adin-cut.c:1416,1444) and the first never (the DS_BUFFER is made once, m_adin.c:216): the program
  * carries filter state from one file into the next, hence the two bits of jamd_adin_reset().  ds48to16_new() leaves the
  * filter history uninitialised; here the samples before the stream start are 0.0.
- * NOT SERVED: silence cutting (-cutsilence, -lv, zero-cross counting). */
+ * Silence cutting (-cutsilence, -lv, zero-cross counting) is the next stage: jamd_adin_cut_*, below. */
 typedef struct {
   int   down48;                  /* -48: the input is 48 kHz                                              */
   const double *fir_3to4;        /* the caller's lpfcoef_3to4[] (n_3to4 entries) and lpfcoef_2to1[]: from */
@@ -936,6 +937,79 @@ int  jamd_adin_push_host(jamd_adin *a, const int16_t *samples, const int64_t *in
 /* One channel after everything queued so far (waits for the device): sub_zmean()'s zlen and zmean, and per FIR stage the
  * inputs arrived and the outputs handed on since the last JAMD_ADIN_DS reset ([3] each).  Any pointer may be NULL. */
 int  jamd_adin_state_get(jamd_adin *a, int chan, int *zlen, float *zmean, int64_t *arrived, int64_t *emitted);
+
+/* ---- silence cutting between jamd_adin and the live front end: -cutsilence, -lv, -zc, -headmargin, -tailmargin ----
+ * The rest of adin_cut() (libjulius/src/adin-cut.c:600-984) around count_zc_e() (libsent/src/adin/zc-e.c): the
+ * conditioned stream of a channel is walked in blocks of chunk_size samples however the pushes cut it; a block whose
+ * zero-cross count over the last c_length samples passes the threshold triggers; the head margin comes out of the cycle
+ * buffer, the tail margin is delivered, blocks behind it wait in the swap buffer for a re-trigger, and nc_max blocks
+ * below the threshold end the segment.  What the reference would have passed to ad_process() after the samples given so
+ * far is delivered, in its order, bit for bit.  Every delivery is a contiguous range of the stream, so the device keeps
+ * per channel the last max(c_length, sbsize) + chunk_size samples (with their running crossing count) and copies
+ * ranges; cbuf / swapbuf have no copies.  Per channel it also keeps is_valid_data, nc, rest_tail, sblen, the trigger
+ * state of count_zc_e() and the samples of an incomplete block.
+ * NOT SERVED: -fvad; -rejectshort / -powerthres; segmentation asked for by the recogniser (ad_process() returning 1) or
+ * by MAXSPEECHLEN; last_trigger_len beyond part_start; audio files in jamd_batch.  Descriptors with which the reference
+ * overruns its swap buffer are refused (jamd_adin_cut_params()). */
+typedef struct {
+  int sfreq;                     /* of the samples given: 16000 behind jamd_adin                          */
+  int level_thres;               /* -lv        (default.c:75-80: 2000)                                    */
+  int zero_cross_num;            /* -zc        (60 per second)                                            */
+  int head_margin_msec;          /* -headmargin (300)                                                     */
+  int tail_margin_msec;          /* -tailmargin (400)                                                     */
+  int chunk_size;                /* -chunksize (1000)                                                     */
+} jamd_adin_cut_desc;
+typedef struct jamd_adin_cut jamd_adin_cut;
+
+int  jamd_adin_cut_default(jamd_adin_cut_desc *d);           /* 16000, 2000, 60, 300, 400, 1000 */
+/* host only: adin_setup_param()'s c_length, noise_zerocross, nc_max and sbsize in its arithmetic (any pointer may be
+ * NULL).  JAMD_EINVAL for sfreq <= 0, chunk_size < 1, chunk_size > c_length (as the reference), negative margins or
+ * counts, sizes beyond 2^24, and where (nc_max - ceil((sbsize - c_length) / chunk_size)) * chunk_size > sbsize: there
+ * the reference logs "swap buffer for re-triggering overflow" and writes past swapbuf (-headmargin 30 -tailmargin 40
+ * -chunksize 480 is one). */
+int  jamd_adin_cut_params(const jamd_adin_cut_desc *d, int *c_length, int *noise_zerocross, int *nc_max, int *sbsize);
+/* nchan channels, each as need_init leaves it.  JAMD_EINVAL where jamd_adin_cut_params() refuses. */
+int  jamd_adin_cut_create(jamd_engine *e, const jamd_adin_cut_desc *d, int nchan, jamd_adin_cut **out);
+void jamd_adin_cut_destroy(jamd_adin_cut *k);
+/* The channels with a non-zero byte of mask ([nchan], host; NULL = all) go back to the start.  Queued on `stream`. */
+int  jamd_adin_cut_reset(jamd_adin_cut *k, const unsigned char *mask, void *stream);
+/* host only: upper bounds of the samples one channel can be handed in a push of `chunk` samples, and of its parts.
+ * With B = (chunk + chunk_size - 1) / chunk_size + 1 blocks at the most (a full carry, a short last block) and triggers,
+ * like ends, nc_max + 1 blocks apart, E = 1 + (B - 1) / (nc_max + 1) of either fit into a push:
+ *   samples  chunk + (chunk_size - 1) + sbsize + E * c_length   (a second trigger's head margin delivers again what
+ *            the tail before it has delivered; for E = 1 this is chunk + (chunk_size - 1) + c_length + sbsize)
+ *   parts    E + 1
+ * Negative (JAMD_EINVAL) for a refused descriptor or chunk < 0. */
+int64_t jamd_adin_cut_push_cap (const jamd_adin_cut_desc *d, int64_t chunk);
+int64_t jamd_adin_cut_parts_cap(const jamd_adin_cut_desc *d, int64_t chunk);
+/* Channel c appends [in_off[c], in_off[c+1]) of dev_in (host offsets [nchan + 1]): what jamd_adin_push_dev() returns, or
+ * raw samples.  A non-zero byte of eos ([nchan], host; NULL = none) ends the channel's stream behind this chunk: the
+ * remainder is processed as one short block, an open segment closes and the channel is as created.  A channel with an
+ * empty chunk and a zero byte is untouched.
+ * A channel's deliveries are cut into parts at each segment end: an ended segment closes its part (which may be empty:
+ * the block that ends a segment is never delivered), so a segment can only open at a part's beginning.  dev_out (room:
+ * the sum of jamd_adin_cut_push_cap()) holds part 0 of channels 0 ... nchan-1 back to back, then part 1, and so on; per
+ * part p, host tables with max_parts rows of room:
+ *   part_off  [p * (nchan + 1) + c]  int64: where channel c's samples of the part begin; entry nchan: where the part ends
+ *   part_final[p * nchan + c]        1: the channel's segment ends behind this part (by silence, or by eos)
+ *   part_start[p * nchan + c]        the stream index (samples given to the channel since its last reset) of the first
+ *                                    sample of a segment that opens in this part, else -1
+ * Row p of part_off and part_final are the sample_off and final of one jamd_frontend_live_push_dev() over dev_out.
+ * *nparts is the number of parts in use (0 where nothing was delivered and nothing ended).  The part count is data: the
+ * call waits once on `stream` for the tables.  If more than max_parts are needed it returns JAMD_EINVAL with *nparts set
+ * and nothing changed: no state has moved, the push can be repeated with more room.  One stream per object. */
+int  jamd_adin_cut_push_dev (jamd_adin_cut *k, const int16_t *dev_in, const int64_t *in_off, const unsigned char *eos,
+                             int16_t *dev_out, int max_parts, int *nparts, int64_t *part_off, unsigned char *part_final,
+                             int64_t *part_start, void *stream);
+/* The same from and to host memory, on the engine's stream; `out` has room for the sum of jamd_adin_cut_push_cap(). */
+int  jamd_adin_cut_push_host(jamd_adin_cut *k, const int16_t *samples, const int64_t *in_off, const unsigned char *eos,
+                             int16_t *out, int max_parts, int *nparts, int64_t *part_off, unsigned char *part_final,
+                             int64_t *part_start);
+/* One channel after everything queued so far (waits for the device): is_valid_data, nc, rest_tail, sblen, the
+ * zero-cross count of the last block, the samples waiting for their block to fill, and the samples given since the last
+ * reset.  Any pointer may be NULL. */
+int  jamd_adin_cut_state_get(jamd_adin_cut *k, int chan, int *is_valid, int *nc, int *rest_tail, int *sblen,
+                             int *zero_cross, int *carried, int64_t *stream_pos);
 
 #ifdef __cplusplus
 }

@@ -1,0 +1,74 @@
+// adin_cut_host.h -- the host side of the silence cutting stage (jamd_adin_cut): the object, which adin_cut_api.hip
+// builds and owns (validation, the table of a push, scratch, the C ABI), and the launchers through which it reaches the
+// kernels in adin_cut.hip.  The API unit launches nothing itself; a launcher checks nothing.  What needs no device is in
+// adin_cut_plan.h.  Internal, not installed.
+#pragma once
+#include "frontend_host.h"
+#include "adin_cut_plan.h"
+
+// One channel between pushes.  `pos` counts the samples given since the last reset; the last `carried` of them wait for
+// their block to fill.  count_zc_e() runs ahead of the blocks: `trig` (is_trig * 2 + (sign == ZC_NEGATIVE)) and `cum`
+// (crossings so far, modulo 2^32) stand behind sample pos - 1, `zc` is the count the last block returned.
+struct AcState { long long pos; unsigned cum; int trig, is_valid, nc, rest_tail, sblen, zc, carried; };
+// One channel in a push: n samples at src_off of the input, their running counts at cnt_off of the scratch
+struct AcChanTab { long long src_off, cnt_off; int n, eos; };
+// The numbers the kernels take
+struct AcDev { int trigger, chunk, c_length, noise_zc, nc_max, sbsize, hist, nchan; };
+
+constexpr int kAcTile = 1024;                // samples per step of the scan workgroup
+constexpr int kAcCopyTile = 2048;            // samples per workgroup of the gather
+
+// What a push leaves on the device for the host, one allocation, one copy: the part count, then for `cap` parts
+// part_off [cap][nchan + 1], part_start [cap][nchan] (int64 each), part_final [cap][nchan] (bytes).
+struct AcTabs {
+  long long *nparts, *off, *start;
+  unsigned char *fin;
+};
+static inline size_t ac_tabs_bytes(int nchan, int cap) {
+  return sizeof(long long) * (1 + (size_t)cap * (nchan + 1) + (size_t)cap * nchan) + (size_t)cap * nchan;
+}
+static inline AcTabs ac_tabs_at(void *base, int nchan, int cap) {
+  AcTabs t;
+  t.nparts = (long long *)base;
+  t.off = t.nparts + 1;
+  t.start = t.off + (size_t)cap * (nchan + 1);
+  t.fin = (unsigned char *)(t.start + (size_t)cap * nchan);
+  return t;
+}
+
+struct jamd_adin_cut {
+  jamd_engine *eng = nullptr;
+  jamd_adin_cut_desc d{};
+  AcParams p{};
+  AcDev g{};
+  int nchan = 0;
+  AcState *d_state = nullptr, *d_next = nullptr;   // [nchan]: between pushes; what the push in flight will leave
+  int16_t *d_hs = nullptr;                   // [nchan][hist] stream sample q in slot q % hist
+  unsigned *d_hc = nullptr;                  // [nchan][hist] crossings among samples 0 ... q, likewise
+  int *d_strig = nullptr;                    // [nchan] count_zc_e()'s state behind the push's last sample
+  unsigned *d_scum = nullptr;                // [nchan]
+  unsigned char *d_mask = nullptr;           // [nchan]
+  // scratch of a push
+  unsigned *d_cnt = nullptr; size_t cnt_cap = 0;           // the running count behind every new sample
+  long long *d_pa = nullptr; size_t pa_cap = 0;            // [cap][nchan] where in the stream a part's range begins
+  int *d_pl = nullptr; size_t pl_cap = 0;                  // [cap][nchan] its length
+  int *d_used = nullptr;                     // [nchan] parts the channel needs
+  char *d_tabs = nullptr; size_t tabs_cap = 0;             // AcTabs
+  char *h_tabs = nullptr; size_t h_tabs_cap = 0;           // pinned
+  FePinned tab;                              // AcChanTab [nchan]
+  int16_t *d_hin = nullptr, *d_hout = nullptr; size_t hin_cap = 0, hout_cap = 0;   // push_host
+};
+
+// ---- adin_cut.hip
+// count_zc_e() over every channel's new samples -> k->d_cnt, k->d_strig / d_scum; the blocks of every channel ->
+// k->d_next, the parts' ranges (k->d_pa / d_pl / d_used) and flags; the part-major offsets and the part count -> `t`
+// (on the device, `cap` parts of room).  Moves no state.
+JAMD_FE_LOCAL int ac_launch_plan(jamd_adin_cut *k, hipStream_t st, const AcChanTab *d_tab, const int16_t *dev_in, AcTabs t,
+                                 int cap);
+// The ranges of nparts parts, none longer than max_len (> 0), -> dev_out
+JAMD_FE_LOCAL int ac_launch_gather(jamd_adin_cut *k, hipStream_t st, const AcChanTab *d_tab, const int16_t *dev_in, AcTabs t,
+                                   int cap, int nparts, int max_len, int16_t *dev_out);
+// After everything has read the old history: the new samples and counts enter it, k->d_next becomes k->d_state
+JAMD_FE_LOCAL int ac_launch_advance(jamd_adin_cut *k, hipStream_t st, const AcChanTab *d_tab, const int16_t *dev_in);
+// The channels d_mask names (NULL: all) back to the start
+JAMD_FE_LOCAL int ac_launch_reset(jamd_adin_cut *k, hipStream_t st, const unsigned char *d_mask);

@@ -82,6 +82,13 @@ class AdinDesc(C.Structure):
 
 ADIN_DS, ADIN_ZMEAN = 1, 2
 
+
+class AdinCutDesc(C.Structure):
+    """jamd_adin_cut_desc (include/julius_amd.h): -lv / -zc / -headmargin / -tailmargin / -chunksize of -cutsilence."""
+    _fields_ = [("sfreq", C.c_int), ("level_thres", C.c_int), ("zero_cross_num", C.c_int), ("head_margin_msec", C.c_int),
+                ("tail_margin_msec", C.c_int), ("chunk_size", C.c_int)]
+
+
 _lib = None
 
 
@@ -228,6 +235,16 @@ def load():
         "jamd_adin_push_dev": (ci, [vp, vp, vp, vp, vp, vp]),
         "jamd_adin_push_host": (ci, [vp, vp, vp, vp, vp]),
         "jamd_adin_state_get": (ci, [vp, ci, vp, vp, vp, vp]),
+        "jamd_adin_cut_default": (ci, [P(AdinCutDesc)]),
+        "jamd_adin_cut_params": (ci, [P(AdinCutDesc), vp, vp, vp, vp]),
+        "jamd_adin_cut_create": (ci, [vp, P(AdinCutDesc), ci, P(vp)]),
+        "jamd_adin_cut_destroy": (None, [vp]),
+        "jamd_adin_cut_reset": (ci, [vp, vp, vp]),
+        "jamd_adin_cut_push_cap": (C.c_int64, [P(AdinCutDesc), C.c_int64]),
+        "jamd_adin_cut_parts_cap": (C.c_int64, [P(AdinCutDesc), C.c_int64]),
+        "jamd_adin_cut_push_dev": (ci, [vp, vp, vp, vp, vp, ci, vp, vp, vp, vp, vp]),
+        "jamd_adin_cut_push_host": (ci, [vp, vp, vp, vp, vp, ci, vp, vp, vp, vp]),
+        "jamd_adin_cut_state_get": (ci, [vp, ci, vp, vp, vp, vp, vp, vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -1215,6 +1232,127 @@ class Adin:
     def close(self):
         if getattr(self, "h", None):
             load().jamd_adin_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class AdinCut:
+    """Silence cutting between Adin and LiveFrontend (jamd_adin_cut): the trigger / head margin / tail margin / swap
+    buffer logic of adin_cut() (libjulius/src/adin-cut.c:600-984) around count_zc_e(), for many channels per call, with
+    every channel's state and the last samples of its stream kept on the device.  A push hands back the samples the
+    reference would have passed on by then, cut into parts at segment ends; each part's row of offsets and final flags
+    is one LiveFrontend.push_dev()."""
+
+    def __init__(self, eng: Engine, nchan: int, desc: "AdinCutDesc | None" = None, **fields):
+        self.eng, self.nchan = eng, int(nchan)
+        self.desc = desc if desc is not None else self.desc_for(**fields)
+        h = C.c_void_p()
+        _check(load().jamd_adin_cut_create(eng.h, C.byref(self.desc), self.nchan, C.byref(h)), "jamd_adin_cut_create")
+        self.h = h
+
+    @staticmethod
+    def desc_for(**fields) -> AdinCutDesc:
+        """jamd_adin_cut_default(), then the fields given (sfreq, level_thres, zero_cross_num, head_margin_msec,
+        tail_margin_msec, chunk_size)."""
+        d = AdinCutDesc()
+        _check(load().jamd_adin_cut_default(C.byref(d)), "jamd_adin_cut_default")
+        names = [f[0] for f in AdinCutDesc._fields_]
+        for key, v in fields.items():
+            if key not in names:
+                raise TypeError(f"AdinCutDesc has no field {key!r}")
+            setattr(d, key, int(v))
+        return d
+
+    def params(self):
+        """(c_length, noise_zerocross, nc_max, sbsize) as adin_setup_param() computes them."""
+        v = [C.c_int(0) for _ in range(4)]
+        _check(load().jamd_adin_cut_params(C.byref(self.desc), *[C.addressof(x) for x in v]), "jamd_adin_cut_params")
+        return tuple(x.value for x in v)
+
+    def push_cap(self, chunk: int) -> int:
+        n = load().jamd_adin_cut_push_cap(C.byref(self.desc), int(chunk))
+        if n < 0:
+            _check(n, "jamd_adin_cut_push_cap")
+        return n
+
+    def parts_cap(self, chunk: int) -> int:
+        n = load().jamd_adin_cut_parts_cap(C.byref(self.desc), int(chunk))
+        if n < 0:
+            _check(n, "jamd_adin_cut_parts_cap")
+        return n
+
+    def reset(self, mask=None, stream: int = 0):
+        m = None
+        if mask is not None:
+            m = np.ascontiguousarray(np.asarray(mask).astype(bool), dtype=np.uint8)
+            assert len(m) == self.nchan
+        _check(load().jamd_adin_cut_reset(self.h, m.ctypes.data if m is not None else None, stream or None),
+               "jamd_adin_cut_reset")
+
+    def _eos(self, eos):
+        if eos is None:
+            return None
+        m = np.ascontiguousarray(np.asarray(eos).astype(bool), dtype=np.uint8)
+        assert len(m) == self.nchan
+        return m
+
+    def _tables(self, max_parts):
+        return (np.zeros((max_parts, self.nchan + 1), np.int64), np.zeros((max_parts, self.nchan), np.uint8),
+                np.full((max_parts, self.nchan), -1, np.int64))
+
+    def push_host(self, chunks, eos=None, max_parts=None):
+        """One int16 chunk per channel (empty = none), `eos` marks the channels whose stream ends behind it ->
+        (samples, part_off [nparts][nchan + 1], part_final [nparts][nchan], part_start [nparts][nchan])."""
+        assert len(chunks) == self.nchan
+        samples, off = Frontend._pack(chunks)
+        m = self._eos(eos)
+        lens = [len(c) for c in chunks]
+        if max_parts is None:
+            max_parts = max(self.parts_cap(n) for n in lens)
+        out = np.zeros(sum(self.push_cap(n) for n in lens), np.int16)
+        poff, pfin, pst = self._tables(int(max_parts))
+        np_ = C.c_int(0)
+        _check(load().jamd_adin_cut_push_host(self.h, samples.ctypes.data if len(samples) else None, off.ctypes.data,
+                                              m.ctypes.data if m is not None else None, out.ctypes.data, int(max_parts),
+                                              C.addressof(np_), poff.ctypes.data, pfin.ctypes.data, pst.ctypes.data),
+               "jamd_adin_cut_push_host")
+        n = np_.value
+        total = int(poff[n - 1, -1]) if n else 0
+        return out[:total].copy(), poff[:n].copy(), pfin[:n].copy(), pst[:n].copy()
+
+    def push_dev(self, dev_in: int, in_off, dev_out: int, eos=None, max_parts=None, stream: int = 0):
+        """Device samples in and out; in_off host int64 [nchan + 1].  Returns (part_off [nparts][nchan + 1], part_final
+        [nparts][nchan], part_start [nparts][nchan]): with dev_out, rows of the first two are what
+        LiveFrontend.push_dev() takes as sample_off and final."""
+        off = np.ascontiguousarray(in_off, dtype=np.int64)
+        assert len(off) == self.nchan + 1
+        m = self._eos(eos)
+        if max_parts is None:
+            max_parts = max(self.parts_cap(int(off[c + 1] - off[c])) for c in range(self.nchan))
+        poff, pfin, pst = self._tables(int(max_parts))
+        np_ = C.c_int(0)
+        _check(load().jamd_adin_cut_push_dev(self.h, dev_in or None, off.ctypes.data, m.ctypes.data if m is not None else None,
+                                             dev_out or None, int(max_parts), C.addressof(np_), poff.ctypes.data,
+                                             pfin.ctypes.data, pst.ctypes.data, stream or None), "jamd_adin_cut_push_dev")
+        n = np_.value
+        return poff[:n].copy(), pfin[:n].copy(), pst[:n].copy()
+
+    def state(self, chan: int):
+        """(is_valid, nc, rest_tail, sblen, zero_cross, carried, stream_pos) of one channel, after everything queued."""
+        v = [C.c_int(0) for _ in range(6)]
+        pos = C.c_int64(0)
+        _check(load().jamd_adin_cut_state_get(self.h, int(chan), *[C.addressof(x) for x in v], C.addressof(pos)),
+               "jamd_adin_cut_state_get")
+        return tuple(x.value for x in v) + (pos.value,)
+
+    def close(self):
+        if getattr(self, "h", None):
+            load().jamd_adin_cut_destroy(self.h)
             self.h = None
 
     def __del__(self):
