@@ -3,7 +3,7 @@
 // kernels in adin_cut.hip.  The API unit launches nothing itself; a launcher checks nothing.  What needs no device is in
 // adin_cut_plan.h.  Internal, not installed.
 #pragma once
-#include "frontend_host.h"
+#include "jamd_host.h"
 #include "adin_cut_plan.h"
 
 // One channel between pushes.  `pos` counts the samples given since the last reset; the last `carried` of them wait for
@@ -36,39 +36,39 @@ static inline AcTabs ac_tabs_at(void *base, int nchan, int cap) {
   return t;
 }
 
-struct jamd_adin_cut {
+struct JAMD_LOCAL jamd_adin_cut {
   jamd_engine *eng = nullptr;
   jamd_adin_cut_desc d{};
   AcParams p{};
   AcDev g{};
   int nchan = 0;
-  AcState *d_state = nullptr, *d_next = nullptr;   // [nchan]: between pushes; what the push in flight will leave
-  int16_t *d_hs = nullptr;                   // [nchan][hist] stream sample q in slot q % hist
-  unsigned *d_hc = nullptr;                  // [nchan][hist] crossings among samples 0 ... q, likewise
-  int *d_strig = nullptr;                    // [nchan] count_zc_e()'s state behind the push's last sample
-  unsigned *d_scum = nullptr;                // [nchan]
-  unsigned char *d_mask = nullptr;           // [nchan]
+  JamdDev<AcState> d_state, d_next;          // [nchan]: between pushes; what the push in flight will leave
+  JamdDev<int16_t> d_hs;                     // [nchan][hist] stream sample q in slot q % hist
+  JamdDev<unsigned> d_hc;                    // [nchan][hist] crossings among samples 0 ... q, likewise
+  JamdDev<int> d_strig;                      // [nchan] count_zc_e()'s state behind the push's last sample
+  JamdDev<unsigned> d_scum;                  // [nchan]
+  JamdDev<unsigned char> d_mask;             // [nchan]
   // scratch of a push
-  unsigned *d_cnt = nullptr; size_t cnt_cap = 0;           // the running count behind every new sample
-  long long *d_pa = nullptr; size_t pa_cap = 0;            // [cap][nchan] where in the stream a part's range begins
-  int *d_pl = nullptr; size_t pl_cap = 0;                  // [cap][nchan] its length
-  int *d_used = nullptr;                     // [nchan] parts the channel needs
-  char *d_tabs = nullptr; size_t tabs_cap = 0;             // AcTabs
-  char *h_tabs = nullptr; size_t h_tabs_cap = 0;           // pinned
-  FePinned tab;                              // AcChanTab [nchan]
-  int16_t *d_hin = nullptr, *d_hout = nullptr; size_t hin_cap = 0, hout_cap = 0;   // push_host
+  JamdDev<unsigned> d_cnt;                   // the running count behind every new sample
+  JamdDev<long long> d_pa;                   // [cap][nchan] where in the stream a part's range begins
+  JamdDev<int> d_pl;                         // [cap][nchan] its length
+  JamdDev<int> d_used;                       // [nchan] parts the channel needs
+  JamdDev<char> d_tabs;                      // AcTabs
+  JamdHostBuf h_tabs;                        // the same, brought down
+  JamdPinned tab;                            // AcChanTab [nchan]
+  JamdStage<int16_t, int16_t> stage;         // push_host
 };
 
 // ---- adin_cut.hip
 // count_zc_e() over every channel's new samples -> k->d_cnt, k->d_strig / d_scum; the blocks of every channel ->
 // k->d_next, the parts' ranges (k->d_pa / d_pl / d_used) and flags; the part-major offsets and the part count -> `t`
 // (on the device, `cap` parts of room).  Moves no state.
-JAMD_FE_LOCAL int ac_launch_plan(jamd_adin_cut *k, hipStream_t st, const AcChanTab *d_tab, const int16_t *dev_in, AcTabs t,
+JAMD_LOCAL int ac_launch_plan(jamd_adin_cut *k, hipStream_t st, const AcChanTab *d_tab, const int16_t *dev_in, AcTabs t,
                                  int cap);
 // The ranges of nparts parts, none longer than max_len (> 0), -> dev_out
-JAMD_FE_LOCAL int ac_launch_gather(jamd_adin_cut *k, hipStream_t st, const AcChanTab *d_tab, const int16_t *dev_in, AcTabs t,
+JAMD_LOCAL int ac_launch_gather(jamd_adin_cut *k, hipStream_t st, const AcChanTab *d_tab, const int16_t *dev_in, AcTabs t,
                                    int cap, int nparts, int max_len, int16_t *dev_out);
 // After everything has read the old history: the new samples and counts enter it, k->d_next becomes k->d_state
-JAMD_FE_LOCAL int ac_launch_advance(jamd_adin_cut *k, hipStream_t st, const AcChanTab *d_tab, const int16_t *dev_in);
+JAMD_LOCAL int ac_launch_advance(jamd_adin_cut *k, hipStream_t st, const AcChanTab *d_tab, const int16_t *dev_in);
 // The channels d_mask names (NULL: all) back to the start
-JAMD_FE_LOCAL int ac_launch_reset(jamd_adin_cut *k, hipStream_t st, const unsigned char *d_mask);
+JAMD_LOCAL int ac_launch_reset(jamd_adin_cut *k, hipStream_t st, const unsigned char *d_mask);

@@ -1,4 +1,5 @@
-// dnn.hip -- DNN-HMM state scores on gfx950 (K3/K4): the only place MFMA is used.
+// dnn.hip -- DNN-HMM state scores on gfx950 (K3/K4): the only place MFMA is used.  The kernels and their launchers;
+// the C ABI of jamd_dnn is in dnn_api.hip (dnn_host.h).
 //
 // Replaces dnn_calc_outprob() (libsent/src/phmm/calc_dnn.c:774-868) for a BATCH
 // of frames (the reference is strictly frame-at-a-time, 00readme-DNN.txt:29-34):
@@ -30,25 +31,7 @@
 // fragment reads are conflict free for the instruction's 16-lane groups
 // (MI355X_MICROARCH.md, LDS).
 #include "jamd_device.h"
-
-struct jamd_dnn {
-  jamd_engine *eng = nullptr;
-  int nlayer = 0;
-  std::vector<int> dims;
-  std::vector<float *> d_b;
-  std::vector<float *> d_wr;       // W[l] in residue-major rows (see dnn_layer_rs_kernel), [dims[l+1]][8 * kmp[l]]
-  std::vector<int> kmp;            // per layer input: padded length of one residue segment = ceil(dims[l] / 8 / 8) * 8
-  float *d_xr = nullptr; size_t xr_cap = 0;   // the frames in residue-major rows
-  float *d_prior = nullptr;
-  float *d_zero = nullptr;           // 64 zero bytes: DMA source of out-of-range quads
-  int maxdim = 0;
-  float *d_act[2] = {nullptr, nullptr}; size_t act_cap = 0;
-  float *d_lse = nullptr; size_t lse_cap = 0;
-  float *d_frames = nullptr; size_t frames_cap = 0;
-  float *d_out = nullptr; size_t out_cap = 0;
-  hipStream_t side = nullptr;          // softmax tail of chunk c runs here while chunk c+1's GEMMs run on the caller's stream
-  hipEvent_t ev_gemm[8] = {}, ev_tail = nullptr, ev_start = nullptr;
-};
+#include "dnn_host.h"
 
 namespace {
 using namespace jamd;
@@ -71,19 +54,14 @@ typedef const __attribute__((address_space(1))) void glb_void;
 // Operands are read in "residue-major" rows: row r holds, for l = 0..7, the segment {x[8m + l]: m = 0..K/8-1}
 // padded with zeros to kmp = a multiple of 8 entries; inside each group of eight m the even ones come first
 // (m = 0,2,4,6,1,3,5,7), so that one 16-byte quad is the lower (or upper) half-wave's operand of four consecutive
-// MFMAs (lanes 0-31 supply k, lanes 32-63 the next k of the chain).  The weights are packed once at creation, the
+// MFMAs (lanes 0-31 supply k, lanes 32-63 the next k of the chain).  The weights are packed once at creation (dnn_api.hip), the
 // frames by dnn_pack_rm_kernel, and a hidden layer's epilogue writes its activations directly in this form.
 //
 // LDS tile: 128 rows x 32 floats per operand and buffer; quad c of row r is kept at position c ^ ((r >> 1) & 7):
 // with 128-byte rows the 16 lanes a ds_read_b128 services per cycle ({0-3,12-15,20-27} etc., MI355X_MICROARCH.md)
 // then hit 16 different 16-byte slots of the 256-byte bank window.
-constexpr int RB = 128;                  // block tile: frames and outputs
-constexpr int MS = 32;                   // entries of one residue segment per slab
-
-__device__ __forceinline__ int rm_pos(int m) {           // place of entry m inside its residue segment
-  const int e = m & 7;
-  return (m & ~7) | ((e & 1) ? 4 + (e >> 1) : (e >> 1));
-}
+constexpr int RB = kDnnRowBlock;         // block tile: frames and outputs
+constexpr int MS = kDnnSlab;             // entries of one residue segment per slab
 
 // frames [T][K] (row stride ldx) -> residue-major rows [T][8 * kmp]
 __global__ void __launch_bounds__(256)
@@ -258,7 +236,7 @@ dnn_layer_rs_kernel(const float *__restrict__ Xr, const float *__restrict__ Wr, 
   for (int jt = 0; jt < 2; jt++) {
     const int j = o0 + wn + 32 * jt + rr;
     const float bj = (j < N) ? bias[j] : 0.0f;
-    const int jpos = OUT ? (j & 7) * kmp_out + rm_pos(j >> 3) : j;
+    const int jpos = OUT ? (j & 7) * kmp_out + dnn_rm_pos(j >> 3) : j;
 #pragma unroll
     for (int i = 0; i < 2; i++) {
 #pragma unroll
@@ -341,191 +319,40 @@ dnn_norm_kernel(float *__restrict__ x, const float *__restrict__ lse, const floa
 
 }  // namespace
 
-extern "C" {
-
-int jamd_dnn_create(jamd_engine *e, const jamd_dnn_desc *d, jamd_dnn **out) {
-  if (!e || !d || !out || d->nlayer < 1 || !d->dims || !d->w || !d->b || !d->state_prior) {
-    jamd_set_error("jamd_dnn_create: bad argument");
-    return JAMD_EINVAL;
-  }
-  *out = nullptr;
-  for (int l = 0; l <= d->nlayer; l++) {
-    if (d->dims[l] <= 0) { jamd_set_error("jamd_dnn_create: dims[%d]=%d", l, d->dims[l]); return JAMD_EINVAL; }
-    // dnn_layer_load() insists on 8-element aligned inputs on AVX/FMA hosts
-    // (calc_dnn.c:395) and calc_dnn_fma() would silently drop a tail
-    if (l < d->nlayer && d->dims[l] % 8 != 0) {
-      jamd_set_error("jamd_dnn_create: layer %d input length %d is not a multiple of 8 "
-                     "(same restriction as the reference's SIMD path)", l, d->dims[l]);
-      return JAMD_EINVAL;
-    }
-  }
-  JAMD_HIP(hipSetDevice(e->device));
-  jamd_dnn *n = new jamd_dnn();
-  n->eng = e; n->nlayer = d->nlayer;
-  n->dims.assign(d->dims, d->dims + d->nlayer + 1);
-  for (int v : n->dims) if (v > n->maxdim) n->maxdim = v;
-  for (int l = 0; l < d->nlayer; l++) {
-    float *b = nullptr;
-    JAMD_HIP(hipMalloc(&b, sizeof(float) * n->dims[l + 1]));
-    JAMD_HIP(hipMemcpy(b, d->b[l], sizeof(float) * n->dims[l + 1], hipMemcpyHostToDevice));
-    n->d_b.push_back(b);
-    // the weights as residue-major rows (dnn_layer_rs_kernel)
-    const int K = n->dims[l], N = n->dims[l + 1], kmp = ((K / 8 + 7) / 8) * 8;
-    std::vector<float> wr((size_t)N * 8 * kmp, 0.0f);
-    for (int o = 0; o < N; o++)
-      for (int k = 0; k < K; k++) {
-        const int m = k >> 3, e = m & 7;
-        wr[(size_t)o * 8 * kmp + (size_t)(k & 7) * kmp + ((m & ~7) | ((e & 1) ? 4 + (e >> 1) : (e >> 1)))] = d->w[l][(size_t)o * K + k];
-      }
-    float *dwr = nullptr;
-    JAMD_HIP(hipMalloc(&dwr, sizeof(float) * wr.size()));
-    JAMD_HIP(hipMemcpy(dwr, wr.data(), sizeof(float) * wr.size(), hipMemcpyHostToDevice));
-    n->d_wr.push_back(dwr); n->kmp.push_back(kmp);
-  }
-  const int S = n->dims[d->nlayer];
-  JAMD_HIP(hipMalloc(&n->d_prior, sizeof(float) * S));
-  JAMD_HIP(hipMemcpy(n->d_prior, d->state_prior, sizeof(float) * S, hipMemcpyHostToDevice));
-  JAMD_HIP(hipMalloc(&n->d_zero, 64));
-  JAMD_HIP(hipMemset(n->d_zero, 0, 64));
-  *out = n;
-  return JAMD_OK;
-}
-
-void jamd_dnn_destroy(jamd_dnn *n) {
-  if (!n) return;
-  (void)hipSetDevice(n->eng->device);
-  for (float *p : n->d_wr) (void)hipFree(p);
-  if (n->d_xr) (void)hipFree(n->d_xr);
-  for (float *p : n->d_b) (void)hipFree(p);
-  if (n->side) {
-    (void)hipStreamSynchronize(n->side);
-    for (int i = 0; i < 8; i++) (void)hipEventDestroy(n->ev_gemm[i]);
-    (void)hipEventDestroy(n->ev_tail); (void)hipEventDestroy(n->ev_start);
-    (void)hipStreamDestroy(n->side);
-  }
-  float *ptrs[] = { n->d_prior, n->d_zero, n->d_act[0], n->d_act[1], n->d_lse, n->d_frames, n->d_out };
-  for (float *p : ptrs) if (p) (void)hipFree(p);
-  delete n;
-}
-
-int jamd_dnn_nstate(const jamd_dnn *n) { return n ? n->dims[n->nlayer] : -1; }
-int jamd_dnn_veclen(const jamd_dnn *n) { return n ? n->dims[0] : -1; }
-
-int jamd_dnn_outprob_dev(jamd_dnn *n, const float *dev_frames, int T, float *dev_out, void *stream) {
-  if (!n || !dev_frames || !dev_out || T < 0) {
-    jamd_set_error("jamd_dnn_outprob_dev: bad argument");
-    return JAMD_EINVAL;
-  }
-  if (T == 0) return JAMD_OK;
-  JAMD_HIP(hipSetDevice(n->eng->device));
-  hipStream_t st = jamd_stream(n->eng, stream);
-  int rc;
-  // hidden activations ping-pong between two [T][maxhidden] buffers
-  int maxh = 1;
-  for (int l = 1; l < n->nlayer; l++) if (8 * n->kmp[l] > maxh) maxh = 8 * n->kmp[l];
-  if ((rc = jamd_grow(&n->d_xr, &n->xr_cap, sizeof(float) * (size_t)T * 8 * n->kmp[0])) != JAMD_OK) return rc;
-  const size_t need = sizeof(float) * (size_t)T * maxh;
-  if (n->act_cap < need) {
-    for (int k = 0; k < 2; k++) { if (n->d_act[k]) JAMD_HIP(hipFree(n->d_act[k])); n->d_act[k] = nullptr; }
-    n->act_cap = 0;
-    JAMD_HIP(hipMalloc(&n->d_act[0], need));
-    JAMD_HIP(hipMalloc(&n->d_act[1], need));
-    n->act_cap = need;
-  }
-  if ((rc = jamd_grow(&n->d_lse, &n->lse_cap, sizeof(float) * (size_t)T)) != JAMD_OK) return rc;
-  // The output layer is followed by the serial row log-sum (dnn_lse: one lane per frame, a
-  // latency-bound chain of table gathers that keeps ~1 wave per CU busy) and the
-  // normalisation.  For very long batches (>= 131072 frames) the frames are cut into up to 8 chunks of 32768+ frames; chunk c's tail
-  // runs on a side stream and overlaps chunk c+1's GEMMs, whose blocks leave registers and
-  // issue slots free for it.
+// ---- launchers (dnn_host.h)
+int dnn_launch_layers(jamd_dnn *n, hipStream_t st, const float *dev_frames, int t0, int Tc, float *dev_out) {
   const int S = n->dims[n->nlayer];
-  int nchunk = T >= 131072 ? (T + 32767) / 32768 : 1;  // measured: pays (+4.5 %) only for very long batches
-  if (nchunk > 8) nchunk = 8;
-#ifdef JAMD_DEV
-  if (getenv("JAMD_DNN_NOCHUNK")) nchunk = 1;
-#endif
-  int per = ((T + nchunk - 1) / nchunk + RB - 1) / RB * RB;
-  if (nchunk > 1 && n->side == nullptr) {
-    JAMD_HIP(hipStreamCreateWithFlags(&n->side, hipStreamNonBlocking));
-    for (int i = 0; i < 8; i++) JAMD_HIP(hipEventCreateWithFlags(&n->ev_gemm[i], hipEventDisableTiming));
-    JAMD_HIP(hipEventCreateWithFlags(&n->ev_tail, hipEventDisableTiming));
-    JAMD_HIP(hipEventCreateWithFlags(&n->ev_start, hipEventDisableTiming));
-  }
-  if (nchunk > 1) {     // the side stream must not start before earlier work on the caller's stream
-    JAMD_HIP(hipEventRecord(n->ev_start, st));
-    JAMD_HIP(hipStreamWaitEvent(n->side, n->ev_start, 0));
-  }
-  for (int c = 0, t0 = 0; t0 < T; c++, t0 += per) {
-    const int Tc = (T - t0 < per) ? T - t0 : per;
-    {
-      const int L0 = 8 * n->kmp[0], nmb = (Tc + RB - 1) / RB;
-      float *xr = n->d_xr + (size_t)t0 * L0;
-      hipLaunchKernelGGL(dnn_pack_rm_kernel, dim3((L0 + 255) / 256, Tc < 16384 ? Tc : 16384), dim3(256), 0, st,
-                         dev_frames + (size_t)t0 * n->dims[0], xr, Tc, n->dims[0], n->dims[0], n->kmp[0]);
-      const float *src = xr;
-      for (int l = 0; l < n->nlayer; l++) {
-        const int N = n->dims[l + 1];
-        const bool last = (l == n->nlayer - 1);
-        const int kout = last ? 0 : n->kmp[l + 1];
-        const int ncover = last ? N : (8 * kout > N ? 8 * kout : N);
-        float *dst = last ? dev_out + (size_t)t0 * S : n->d_act[l & 1];
-        const int nnb = (ncover + RB - 1) / RB;
-        const int grid = 8 * ((nnb + 7) / 8) * nmb;
-        const bool straddle = (n->kmp[l] % MS) != 0;     // segments that are not whole slabs: stream the row (see the kernel)
+  const int L0 = 8 * n->kmp[0], nmb = (Tc + RB - 1) / RB;
+  float *xr = n->d_xr + (size_t)t0 * L0;
+  hipLaunchKernelGGL(dnn_pack_rm_kernel, dim3((L0 + 255) / 256, Tc < 16384 ? Tc : 16384), dim3(256), 0, st,
+                     dev_frames + (size_t)t0 * n->dims[0], xr, Tc, n->dims[0], n->dims[0], n->kmp[0]);
+  const float *src = xr;
+  for (int l = 0; l < n->nlayer; l++) {
+    const int N = n->dims[l + 1];
+    const bool last = (l == n->nlayer - 1);
+    const int kout = last ? 0 : n->kmp[l + 1];
+    const int ncover = last ? N : (8 * kout > N ? 8 * kout : N);
+    float *dst = last ? dev_out + (size_t)t0 * S : n->d_act[l & 1];
+    const int nnb = (ncover + RB - 1) / RB;
+    const int grid = 8 * ((nnb + 7) / 8) * nmb;
+    const bool straddle = (n->kmp[l] % MS) != 0;     // segments that are not whole slabs: stream the row (see the kernel)
 #define JAMD_DNN_LAYER(OUT_, STR_, LDY_, KOUT_)                                                                          \
-        hipLaunchKernelGGL((dnn_layer_rs_kernel<OUT_, STR_>), dim3(grid), dim3(256), 0, st, src, n->d_wr[l], n->d_b[l], \
-                           n->eng->d_logistic, dst, Tc, n->kmp[l], N, ncover, LDY_, KOUT_, nmb, n->d_zero)
-        if (last) { if (straddle) JAMD_DNN_LAYER(0, true, N, 0); else JAMD_DNN_LAYER(0, false, N, 0); }
-        else { if (straddle) JAMD_DNN_LAYER(1, true, 8 * kout, kout); else JAMD_DNN_LAYER(1, false, 8 * kout, kout); }
+    hipLaunchKernelGGL((dnn_layer_rs_kernel<OUT_, STR_>), dim3(grid), dim3(256), 0, st, src, n->d_wr[l], n->d_b[l], \
+                       n->eng->d_logistic, dst, Tc, n->kmp[l], N, ncover, LDY_, KOUT_, nmb, n->d_zero)
+    if (last) { if (straddle) JAMD_DNN_LAYER(0, true, N, 0); else JAMD_DNN_LAYER(0, false, N, 0); }
+    else { if (straddle) JAMD_DNN_LAYER(1, true, 8 * kout, kout); else JAMD_DNN_LAYER(1, false, 8 * kout, kout); }
 #undef JAMD_DNN_LAYER
-        src = dst;
-      }
-    }
-    hipStream_t ts = st;
-    if (nchunk > 1) {
-      JAMD_HIP(hipEventRecord(n->ev_gemm[c], st));
-      JAMD_HIP(hipStreamWaitEvent(n->side, n->ev_gemm[c], 0));
-      ts = n->side;
-    }
-    float *oc = dev_out + (size_t)t0 * S;
-    hipLaunchKernelGGL(dnn_lse_kernel, dim3((Tc + 63) / 64), dim3(64), 0, ts, oc, n->eng->d_addlog,
-                       n->d_lse + t0, Tc, S, n->eng->addmin_f);
-    hipLaunchKernelGGL(dnn_norm_kernel, dim3((S + 1023) / 1024, Tc < 4096 ? Tc : 4096), dim3(256), 0, ts, oc,
-                       n->d_lse + t0, n->d_prior, Tc, S);
-  }
-  if (nchunk > 1) {     // join: the caller's stream continues only after the last tail
-    JAMD_HIP(hipEventRecord(n->ev_tail, n->side));
-    JAMD_HIP(hipStreamWaitEvent(st, n->ev_tail, 0));
-  }
-  hipError_t le = hipGetLastError();
-  if (le != hipSuccess) {
-    jamd_set_error("jamd_dnn_outprob_dev: launch failed: %s", hipGetErrorString(le));
-    return JAMD_ELAUNCH;
+    src = dst;
   }
   return JAMD_OK;
 }
 
-int jamd_dnn_outprob_host(jamd_dnn *n, const float *host_frames, int T, float *host_out) {
-  if (!n || !host_frames || !host_out || T < 0) {
-    jamd_set_error("jamd_dnn_outprob_host: bad argument");
-    return JAMD_EINVAL;
-  }
-  if (T == 0) return JAMD_OK;
-  JAMD_HIP(hipSetDevice(n->eng->device));
-  const int D = n->dims[0], S = n->dims[n->nlayer];
-  int rc;
-  if ((rc = jamd_grow(&n->d_frames, &n->frames_cap, sizeof(float) * (size_t)T * D)) != JAMD_OK) return rc;
-  if ((rc = jamd_grow(&n->d_out, &n->out_cap, sizeof(float) * (size_t)T * S)) != JAMD_OK) return rc;
-  hipStream_t st = n->eng->stream;
-  JAMD_HIP(hipMemcpyAsync(n->d_frames, host_frames, sizeof(float) * (size_t)T * D, hipMemcpyHostToDevice, st));
-  if ((rc = jamd_dnn_outprob_dev(n, n->d_frames, T, n->d_out, st)) != JAMD_OK) return rc;
-  JAMD_HIP(hipMemcpyAsync(host_out, n->d_out, sizeof(float) * (size_t)T * S, hipMemcpyDeviceToHost, st));
-  hipError_t se = hipStreamSynchronize(st);
-  if (se != hipSuccess) {
-    jamd_set_error("jamd_dnn_outprob_host: execution failed: %s", hipGetErrorString(se));
-    return JAMD_ELAUNCH;
-  }
+int dnn_launch_tail(jamd_dnn *n, hipStream_t ts, int t0, int Tc, float *dev_out) {
+  const int S = n->dims[n->nlayer];
+  float *oc = dev_out + (size_t)t0 * S;
+  hipLaunchKernelGGL(dnn_lse_kernel, dim3((Tc + 63) / 64), dim3(64), 0, ts, oc, n->eng->d_addlog,
+                     n->d_lse + t0, Tc, S, n->eng->addmin_f);
+  hipLaunchKernelGGL(dnn_norm_kernel, dim3((S + 1023) / 1024, Tc < 4096 ? Tc : 4096), dim3(256), 0, ts, oc,
+                     n->d_lse + t0, n->d_prior, Tc, S);
   return JAMD_OK;
 }
-
-}  // extern "C"

@@ -8,6 +8,7 @@
 // expressions on the host and uploads the tables.
 #include "jamd_internal.h"
 #include <cmath>
+#include <memory>
 #include <mutex>
 
 static thread_local char g_err[512] = "";
@@ -61,7 +62,8 @@ int jamd_engine_create(int device, jamd_engine **out) {
                    device, prop.gcnArchName);
     return JAMD_ENODEV;
   }
-  jamd_engine *e = new jamd_engine();
+  // (released through jamd_engine_destroy() by any return before the hand-over)
+  std::unique_ptr<jamd_engine, void (*)(jamd_engine *)> e(new jamd_engine(), jamd_engine_destroy);
   e->device = device;
   e->num_cu = prop.multiProcessorCount;
   JAMD_HIP(hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking));
@@ -90,7 +92,7 @@ int jamd_engine_create(int device, jamd_engine **out) {
   float th = (float)JAMD_LOG_ADDMIN;
   if ((double)th < JAMD_LOG_ADDMIN) th = nextafterf(th, INFINITY);
   e->addmin_f = th;
-  *out = e;
+  *out = e.release();
   return JAMD_OK;
 }
 

@@ -387,7 +387,7 @@ int fe_launch_frames(jamd_frontend *f, hipStream_t st, const int16_t *dev_sample
 int fe_launch_noise(jamd_frontend *f, hipStream_t st, const int16_t *dev_samples, const long long *d_soff,
                     const int *d_hoff, int nutt, int Htot, float *dev_noise) {
   int rc;
-  if ((rc = jamd_grow(&f->d_mag, &f->mag_cap, (size_t)Htot * f->tb.fftN * sizeof(double))) != JAMD_OK) return rc;
+  if ((rc = f->d_mag.grow((size_t)Htot * f->tb.fftN * sizeof(double))) != JAMD_OK) return rc;
   FeParams p = f->p;
   p.nutt = nutt;
   hipLaunchKernelGGL(fe_noise_frame, dim3((Htot + f->fpb - 1) / f->fpb), dim3(64 * f->fpb), f->lds, st, p, dev_samples,

@@ -8,7 +8,7 @@
 
 static int lv_refuse_ss_calc(jamd_frontend_live *l, const char *who) {
   if (l->f->ss_mode != JAMD_SS_CALC) return JAMD_OK;
-  return fe_refuse("%s: JAMD_SS_CALC is set on the parent front end: a live segment has no head known in advance (use "
+  return jamd_refuse("%s: JAMD_SS_CALC is set on the parent front end: a live segment has no head known in advance (use "
                    "JAMD_SS_LOAD or JAMD_SS_OFF)", who);
 }
 
@@ -18,9 +18,9 @@ static int lv_refuse_ss_calc(jamd_frontend_live *l, const char *who) {
 static int lv_base_frames(jamd_frontend *f, hipStream_t st, const int16_t *dev_samples, const int64_t *sample_off, int nchan,
                           long long B, std::initializer_list<const std::vector<int> *> tabs, const int **d_tabs) {
   int rc;
-  if ((rc = jamd_grow(&f->d_stat, &f->stat_cap, (size_t)(B > 0 ? B : 1) * f->d.baselen * sizeof(float))) != JAMD_OK) return rc;
+  if ((rc = f->d_stat.grow((size_t)(B > 0 ? B : 1) * f->d.baselen * sizeof(float))) != JAMD_OK) return rc;
   if ((rc = fe_put_offsets(f, st, sample_off, nchan, tabs)) != JAMD_OK) return rc;
-  const long long *d_soff = (const long long *)f->off.d;
+  const long long *d_soff = (const long long *)f->off.d.p;
   *d_tabs = (const int *)(d_soff + nchan + 1);
   return B > 0 ? fe_launch_frames(f, st, dev_samples, d_soff, *d_tabs, nchan, (int)B) : JAMD_OK;
 }
@@ -28,7 +28,7 @@ static int lv_base_frames(jamd_frontend *f, hipStream_t st, const int16_t *dev_s
 extern "C" {
 
 int jamd_frontend_live_default(jamd_frontend_live_desc *d) {
-  if (!d) return fe_refuse("jamd_frontend_live_default: d is NULL");
+  if (!d) return jamd_refuse("jamd_frontend_live_default: d is NULL");
   d->map_cmn = 1; d->map_weight = 100.0f;    // default.c:153-156
   d->cmean_init = nullptr; d->cvar_init = nullptr;
   return JAMD_OK;
@@ -37,24 +37,20 @@ int jamd_frontend_live_default(jamd_frontend_live_desc *d) {
 int jamd_frontend_live_frames(const jamd_frontend_desc *d, int64_t nsamples) {
   if (!d || d->framesize < 1 || d->frameshift < 1 || d->splice < 1 || (d->delta && d->delWin < 1) ||
       (d->acc && d->accWin < 1))
-    return fe_refuse("jamd_frontend_live_frames: NULL descriptor, or framesize / frameshift / splice / window < 1");
+    return jamd_refuse("jamd_frontend_live_frames: NULL descriptor, or framesize / frameshift / splice / window < 1");
   const long long T = lv_counts(*d, nsamples).To;
   return T > 0x7fffffff ? 0x7fffffff : (int)T;
 }
 
 void jamd_frontend_live_destroy(jamd_frontend_live *l) {
   if (!l) return;
-  for (void *q : {l->state, (void *)l->d_feat, (void *)l->d_upd, (void *)l->stage.d_in, (void *)l->stage.d_out,
-                  (void *)l->d_stage, (void *)l->d_hist})
-    (void)hipFree(q);
-  fe_pin_free(&l->tab);
-  delete l;
+  delete l;                                  // (the parent is not looked at: it may have gone first)
 }
 
 int jamd_frontend_live_state_set(jamd_frontend_live *l, int chan, const float *cmean, const float *cvar) {
   if (!l || !cmean || chan < 0 || chan >= l->nchan)
-    return fe_refuse("jamd_frontend_live_state_set: NULL argument or channel out of range");
-  if (l->p.var && !cvar) return fe_refuse("jamd_frontend_live_state_set: the kind has cvn: a variance is needed");
+    return jamd_refuse("jamd_frontend_live_state_set: NULL argument or channel out of range");
+  if (l->p.var && !cvar) return jamd_refuse("jamd_frontend_live_state_set: the kind has cvn: a variance is needed");
   if (!l->open.empty() && l->open[chan]) {
     jamd_set_error("jamd_frontend_live_state_set: channel %d has an open segment (end it with a final push first)", chan);
     return JAMD_ESTATE;
@@ -71,7 +67,7 @@ int jamd_frontend_live_state_set(jamd_frontend_live *l, int chan, const float *c
 
 int jamd_frontend_live_state_get(jamd_frontend_live *l, int chan, float *cmean, float *cvar, float *emax, int *flags) {
   if (!l || chan < 0 || chan >= l->nchan)
-    return fe_refuse("jamd_frontend_live_state_get: NULL object or channel out of range");
+    return jamd_refuse("jamd_frontend_live_state_get: NULL object or channel out of range");
   JAMD_HIP(hipSetDevice(l->f->eng->device));
   JAMD_HIP(hipDeviceSynchronize());
   const size_t V = l->p.veclen;
@@ -83,21 +79,21 @@ int jamd_frontend_live_state_get(jamd_frontend_live *l, int chan, float *cmean, 
 }
 
 int jamd_frontend_live_create(jamd_frontend *f, const jamd_frontend_live_desc *ld, int nchan, jamd_frontend_live **out) {
-  if (!f || !ld || !out || nchan < 1) return fe_refuse("jamd_frontend_live_create: NULL argument or nchan < 1");
+  if (!f || !ld || !out || nchan < 1) return jamd_refuse("jamd_frontend_live_create: NULL argument or nchan < 1");
   *out = nullptr;
   const jamd_frontend_desc &d = f->d;
   if (d.absesup && d.acc)
-    return fe_refuse("jamd_frontend_live_create: _N together with _A is not served: the reference's flush loop "
+    return jamd_refuse("jamd_frontend_live_create: _N together with _A is not served: the reference's flush loop "
                      "(realtime-1stpass.c:1233-1241) strips the absolute energy before the acceleration buffer, its main "
                      "loop after it, so the last frames of every segment carry a stale slot");
   if (d.frameshift > d.framesize + 1)
-    return fe_refuse("jamd_frontend_live_create: frameshift %d beyond the live window of %d samples (the reference's "
+    return jamd_refuse("jamd_frontend_live_create: frameshift %d beyond the live window of %d samples (the reference's "
                      "window shift has no meaning there)", d.frameshift, d.framesize + 1);
   if (d.cvn && ld->cmean_init && !ld->cvar_init)
-    return fe_refuse("jamd_frontend_live_create: the kind has cvn: an initial mean needs an initial variance");
+    return jamd_refuse("jamd_frontend_live_create: the kind has cvn: an initial mean needs an initial variance");
   if ((long long)nchan * d.veclen > 0x7fffffffLL / kRing)
-    return fe_refuse("jamd_frontend_live_create: %d channels of %d elements are too many", nchan, d.veclen);
-  jamd_frontend_live *l = new jamd_frontend_live();
+    return jamd_refuse("jamd_frontend_live_create: %d channels of %d elements are too many", nchan, d.veclen);
+  std::unique_ptr<jamd_frontend_live> l(new jamd_frontend_live());   // (its members own what they hold)
   l->f = f; l->nchan = nchan;
   LvParams &p = l->p;
   p.nchan = nchan; p.veclen = d.veclen; p.baselen = d.baselen; p.nb = d.baselen - (d.absesup ? 1 : 0);
@@ -114,23 +110,18 @@ int jamd_frontend_live_create(jamd_frontend *f, const jamd_frontend_live_desc *l
   if (p.R < 1) p.R = 1;
   p.fs = d.framesize;
   l->open.assign(nchan, 0); l->ns.assign(nchan, 0);
-  hipError_t e = hipSetDevice(f->eng->device);
   const size_t C = nchan, V = d.veclen, CV = C * V;
   // floats: emax | cmean | cvar | now_sum | now_var | all_var | ring_sum | rmax | ring | sp ;
   // ints: flags now_fn all_fn head cnum cmax | ring_fn ; int16: res
   const size_t nring = C * p.R * d.baselen, nsp = CV * (d.splice - 1), nres = C * d.framesize;
   const size_t nfl = C + 5 * CV + CV * kRing + C + nring + nsp, nin = 6 * C + C * kRing;
   const size_t nstate = nfl * sizeof(float) + nin * sizeof(int) + nres * sizeof(int16_t);
-  if (e == hipSuccess) e = hipMalloc(&l->state, nstate);
-  if (e == hipSuccess) e = hipMalloc((void **)&l->d_upd, C);
-  if (e == hipSuccess) e = hipMemset(l->state, 0, nstate);
-  if (e != hipSuccess) {
-    jamd_set_error("jamd_frontend_live_create: device allocation failed: %s", hipGetErrorString(e));
-    jamd_frontend_live_destroy(l);
-    return e == hipErrorOutOfMemory ? JAMD_ENOMEM : JAMD_ENODEV;
-  }
+  JAMD_HIP(hipSetDevice(f->eng->device));
+  int rc;
+  if ((rc = l->state.alloc(nstate, true)) != JAMD_OK) return rc;
+  if ((rc = l->d_upd.alloc(C)) != JAMD_OK) return rc;
   LvState &s = l->s;
-  float *q = (float *)l->state;
+  float *q = (float *)l->state.p;
   s.emax = q; q += C;
   s.cmean = q; q += CV; s.cvar = q; q += CV; s.now_sum = q; q += CV; s.now_var = q; q += CV; s.all_var = q; q += CV;
   s.ring_sum = q; q += CV * kRing;
@@ -142,29 +133,21 @@ int jamd_frontend_live_create(jamd_frontend *f, const jamd_frontend_live_desc *l
   // energy_max_init(): 5.0; CMN_realtime_new(): clist_max = CPSTEP
   std::vector<float> five(C, 5.0f);
   std::vector<int> step(C, LV_CPSTEP);
-  e = hipMemcpy(s.emax, five.data(), C * sizeof(float), hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(s.cmax, step.data(), C * sizeof(int), hipMemcpyHostToDevice);
-  if (e != hipSuccess) {
-    jamd_set_error("jamd_frontend_live_create: hipMemcpy failed: %s", hipGetErrorString(e));
-    jamd_frontend_live_destroy(l);
-    return JAMD_ENODEV;
-  }
+  JAMD_HIP(hipMemcpy(s.emax, five.data(), C * sizeof(float), hipMemcpyHostToDevice));
+  JAMD_HIP(hipMemcpy(s.cmax, step.data(), C * sizeof(int), hipMemcpyHostToDevice));
   // the tables of a push, so that no push allocates them
-  int rc = fe_pin_begin(&l->tab, sizeof(long long) * (C + 1) + 3 * sizeof(int) * (C + 1));
-  if (rc != JAMD_OK) { jamd_frontend_live_destroy(l); return rc; }
+  if ((rc = l->tab.begin(sizeof(long long) * (C + 1) + 3 * sizeof(int) * (C + 1))) != JAMD_OK) return rc;
   if (ld->cmean_init && (d.cmn || d.cvn)) {
-    for (int c = 0; c < nchan; c++) {
-      rc = jamd_frontend_live_state_set(l, c, ld->cmean_init, ld->cvar_init);
-      if (rc != JAMD_OK) { jamd_frontend_live_destroy(l); return rc; }
-    }
+    for (int c = 0; c < nchan; c++)
+      if ((rc = jamd_frontend_live_state_set(l.get(), c, ld->cmean_init, ld->cvar_init)) != JAMD_OK) return rc;
   }
-  *out = l;
+  *out = l.release();
   return JAMD_OK;
 }
 
 int jamd_frontend_live_run_dev(jamd_frontend_live *l, const int16_t *dev_samples, const int64_t *sample_off,
                                float *dev_out, int *frame_off, void *stream) {
-  if (!l || !dev_samples || !sample_off || !dev_out) return fe_refuse("jamd_frontend_live_run_dev: NULL argument");
+  if (!l || !dev_samples || !sample_off || !dev_out) return jamd_refuse("jamd_frontend_live_run_dev: NULL argument");
   int rc;
   if ((rc = lv_refuse_ss_calc(l, "jamd_frontend_live_run_dev")) != JAMD_OK) return rc;
   if (l->nopen) {
@@ -178,18 +161,18 @@ int jamd_frontend_live_run_dev(jamd_frontend_live *l, const int16_t *dev_samples
   long long B = 0, N = 0, O = 0;
   for (int c = 0; c < nchan; c++) {
     const long long n = fe_span("jamd_frontend_live_run_dev", "channel", sample_off, c, err);
-    if (n < 0) return fe_refuse("%s", err.c_str());
+    if (n < 0) return jamd_refuse("%s", err.c_str());
     const LvCounts k = lv_counts(d, n);
     boff[c] = (int)B; noff[c] = (int)N; ooff[c] = (int)O;
     act[c] = (n > 0 ? kActive | kFinal : 0) | (k.reest ? kReest : 0);
     B += k.Tb; N += k.Nf; O += k.To;
     if ((B + 1) * (long long)d.vecbuflen * d.splice > 0x7fffffffLL)
-      return fe_refuse("jamd_frontend_live_run_dev: batch too large (%lld frames)", B);
+      return jamd_refuse("jamd_frontend_live_run_dev: batch too large (%lld frames)", B);
   }
   boff[nchan] = (int)B; noff[nchan] = (int)N; ooff[nchan] = (int)O;
   JAMD_HIP(hipSetDevice(l->f->eng->device));
   hipStream_t st = jamd_stream(l->f->eng, stream);
-  if ((rc = jamd_grow(&l->d_feat, &l->feat_cap, (size_t)(N > 0 ? N : 1) * d.veclen * sizeof(float))) != JAMD_OK) return rc;
+  if ((rc = l->d_feat.grow((size_t)(N > 0 ? N : 1) * d.veclen * sizeof(float))) != JAMD_OK) return rc;
   const int *d_tabs;                         // (a whole segment: nothing in the ring, frames from 0)
   if ((rc = lv_base_frames(l->f, st, dev_samples, sample_off, nchan, B, {&boff, &noff, &ooff, &act, &zero}, &d_tabs)) != JAMD_OK)
     return rc;
@@ -201,14 +184,14 @@ int jamd_frontend_live_run_dev(jamd_frontend_live *l, const int16_t *dev_samples
 int jamd_frontend_live_push_frames(const jamd_frontend_desc *d, int64_t samples_before, int64_t chunk, int final) {
   if (!d || d->framesize < 1 || d->frameshift < 1 || d->splice < 1 || (d->delta && d->delWin < 1) ||
       (d->acc && d->accWin < 1) || samples_before < 0 || chunk < 0)
-    return fe_refuse("jamd_frontend_live_push_frames: NULL descriptor, framesize / frameshift / splice / window < 1, or a "
+    return jamd_refuse("jamd_frontend_live_push_frames: NULL descriptor, framesize / frameshift / splice / window < 1, or a "
                      "negative sample count");
   const long long T = lv_push(*d, samples_before, chunk, final != 0).rows;
   return T > 0x7fffffff ? 0x7fffffff : (int)T;
 }
 
 int jamd_frontend_live_stream_cap(jamd_frontend_live *l, int max_rows) {
-  if (!l || max_rows < 1) return fe_refuse("jamd_frontend_live_stream_cap: NULL object or max_rows < 1");
+  if (!l || max_rows < 1) return jamd_refuse("jamd_frontend_live_stream_cap: NULL object or max_rows < 1");
   if (l->nopen) {
     jamd_set_error("jamd_frontend_live_stream_cap: %d channel(s) have an open segment", l->nopen);
     return JAMD_ESTATE;
@@ -219,7 +202,7 @@ int jamd_frontend_live_stream_cap(jamd_frontend_live *l, int max_rows) {
 
 int jamd_frontend_live_push_dev(jamd_frontend_live *l, const int16_t *dev_samples, const int64_t *sample_off,
                                 const unsigned char *final, float *dev_out, int *frame_off, void *stream) {
-  if (!l || !sample_off) return fe_refuse("jamd_frontend_live_push_dev: NULL argument");
+  if (!l || !sample_off) return jamd_refuse("jamd_frontend_live_push_dev: NULL argument");
   int rc;
   if ((rc = lv_refuse_ss_calc(l, "jamd_frontend_live_push_dev")) != JAMD_OK) return rc;
   const jamd_frontend_desc &d = l->f->d;
@@ -231,15 +214,15 @@ int jamd_frontend_live_push_dev(jamd_frontend_live *l, const int16_t *dev_sample
   std::vector<char> open_after(l->open);
   const size_t ntab = sizeof(long long) * (nchan + 1) + 3 * sizeof(int) * (nchan + 1);
   JAMD_HIP(hipSetDevice(l->f->eng->device));
-  if ((rc = fe_pin_begin(&l->tab, ntab)) != JAMD_OK) return rc;
-  long long *h_coff = (long long *)l->tab.h;
+  if ((rc = l->tab.begin(ntab)) != JAMD_OK) return rc;
+  long long *h_coff = (long long *)l->tab.h.p;
   int *h_soff = (int *)(h_coff + nchan + 1), *h_rlen = h_soff + nchan + 1, *h_newr = h_rlen + nchan + 1;
   std::string err;
   long long B = 0, N = 0, O = 0, S = 0, need_rows = 0;
   bool any = false;
   for (int c = 0; c < nchan; c++) {
     const long long n = fe_span("jamd_frontend_live_push_dev", "channel", sample_off, c, err);
-    if (n < 0) return fe_refuse("%s", err.c_str());
+    if (n < 0) return jamd_refuse("%s", err.c_str());
     const bool fin = final && final[c], was = l->open[c] != 0;
     boff[c] = (int)B; noff[c] = (int)N; ooff[c] = (int)O;
     soff[c] = S; h_coff[c] = sample_off[c]; h_soff[c] = (int)S; h_rlen[c] = 0; h_newr[c] = 0;
@@ -248,7 +231,7 @@ int jamd_frontend_live_push_dev(jamd_frontend_live *l, const int16_t *dev_sample
     const long long n_old = was ? l->ns[c] : 0;
     const LvPush q = lv_push(d, n_old, n, fin);
     if (keep_rows && q.F_new > l->hist_cap)
-      return fe_refuse("jamd_frontend_live_push_dev: channel %d would hold %lld rows of an open segment, beyond the cap of %d "
+      return jamd_refuse("jamd_frontend_live_push_dev: channel %d would hold %lld rows of an open segment, beyond the cap of %d "
                        "(jamd_frontend_live_stream_cap())", c, q.F_new, l->hist_cap);
     if (q.F_new > need_rows) need_rows = q.F_new;
     act[c] = kActive | (was ? kCont : 0) | (fin ? kFinal : 0) | (q.reest ? kReest : 0);
@@ -258,32 +241,30 @@ int jamd_frontend_live_push_dev(jamd_frontend_live *l, const int16_t *dev_sample
     S += q.r_old + n;
     open_after[c] = !fin; ns_after[c] = fin ? 0 : n_old + n;
     if ((B + 1) * (long long)d.vecbuflen * d.splice > 0x7fffffffLL || S > 0x7fffffffLL || q.Tb_new > 0x7fffffffLL)
-      return fe_refuse("jamd_frontend_live_push_dev: batch too large (%lld frames, %lld samples)", B, S);
+      return jamd_refuse("jamd_frontend_live_push_dev: batch too large (%lld frames, %lld samples)", B, S);
   }
   boff[nchan] = (int)B; noff[nchan] = (int)N; ooff[nchan] = (int)O;
   soff[nchan] = S; h_coff[nchan] = sample_off[nchan]; h_soff[nchan] = (int)S; h_rlen[nchan] = 0; h_newr[nchan] = 0;
   if ((sample_off[nchan] > 0 && !dev_samples) || (O > 0 && !dev_out))
-    return fe_refuse("jamd_frontend_live_push_dev: NULL buffer");
+    return jamd_refuse("jamd_frontend_live_push_dev: NULL buffer");
   if (frame_off) memcpy(frame_off, ooff.data(), sizeof(int) * (nchan + 1));
   if (!any) return JAMD_OK;
   hipStream_t st = jamd_stream(l->f->eng, stream);
-  if ((rc = jamd_grow(&l->d_feat, &l->feat_cap, (size_t)(N > 0 ? N : 1) * d.veclen * sizeof(float))) != JAMD_OK) return rc;
-  if ((rc = jamd_grow(&l->d_stage, &l->stage_cap, (size_t)(S > 0 ? S : 1) * sizeof(int16_t))) != JAMD_OK) return rc;
+  if ((rc = l->d_feat.grow((size_t)(N > 0 ? N : 1) * d.veclen * sizeof(float))) != JAMD_OK) return rc;
+  if ((rc = l->d_stage.grow((size_t)(S > 0 ? S : 1) * sizeof(int16_t))) != JAMD_OK) return rc;
   if (keep_rows && need_rows > l->hist_rows) {
     // the history grows: at least twofold, never beyond the cap; the rows of the open segments move over
     long long rows = 2LL * l->hist_rows > need_rows ? 2LL * l->hist_rows : need_rows;
     if (rows < 256) rows = 256;
     if (rows > l->hist_cap) rows = l->hist_cap;
-    float *nh = nullptr;
-    JAMD_HIP(hipMalloc((void **)&nh, (size_t)nchan * rows * d.veclen * sizeof(float)));
-    if (l->d_hist) {
-      if ((rc = lv_launch_grow(l, st, nh, l->hist_rows, rows)) != JAMD_OK) { (void)hipFree(nh); return rc; }
-      JAMD_HIP(hipFree(l->d_hist));
-    }
-    l->d_hist = nh; l->hist_rows = (int)rows;
+    JamdDev<float> nh;
+    if ((rc = nh.grow((size_t)nchan * rows * d.veclen * sizeof(float))) != JAMD_OK) return rc;
+    if (l->d_hist && (rc = lv_launch_grow(l, st, nh, l->hist_rows, rows)) != JAMD_OK) return rc;
+    l->d_hist.swap(nh);                        // (the old rows go with nh)
+    l->hist_rows = (int)rows;
   }
-  if ((rc = fe_pin_send(&l->tab, ntab, st)) != JAMD_OK) return rc;
-  const long long *d_coff = (const long long *)l->tab.d;
+  if ((rc = l->tab.send(ntab, st)) != JAMD_OK) return rc;
+  const long long *d_coff = (const long long *)l->tab.d.p;
   const int *d_soff = (const int *)(d_coff + nchan + 1);
   const LvPacked pk{l->d_stage, d_coff, d_soff, d_soff + nchan + 1, d_soff + 2 * (nchan + 1)};
   if (S > 0 && (rc = lv_launch_pack(l, st, dev_samples, pk, S)) != JAMD_OK) return rc;
@@ -299,42 +280,44 @@ int jamd_frontend_live_push_dev(jamd_frontend_live *l, const int16_t *dev_sample
 
 int jamd_frontend_live_run_host(jamd_frontend_live *l, const int16_t *samples, const int64_t *sample_off, float *out,
                                 int *frame_off) {
-  if (!l || !samples || !sample_off || !out) return fe_refuse("jamd_frontend_live_run_host: NULL argument");
+  if (!l || !samples || !sample_off || !out) return jamd_refuse("jamd_frontend_live_run_host: NULL argument");
   std::string err;
   long long O = 0;
   for (int c = 0; c < l->nchan; c++) {
     const long long n = fe_span("jamd_frontend_live_run_host", "channel", sample_off, c, err);
-    if (n < 0) return fe_refuse("%s", err.c_str());
+    if (n < 0) return jamd_refuse("%s", err.c_str());
     O += lv_counts(l->f->d, n).To;
   }
-  return fe_host_call(&l->stage, l->f->eng, samples, (size_t)sample_off[l->nchan], out, (size_t)O * l->f->d.veclen * l->f->d.splice,
-                      [&](const int16_t *in, float *o, hipStream_t st) {
-                        return jamd_frontend_live_run_dev(l, in, sample_off, o, frame_off, st);
+  return jamd_host_call(&l->stage, l->f->eng, samples, (size_t)sample_off[l->nchan], out, (size_t)O * l->f->d.veclen * l->f->d.splice,
+                      [&](const int16_t *in, float *o, hipStream_t st) -> long long {
+                        const int rc = jamd_frontend_live_run_dev(l, in, sample_off, o, frame_off, st);
+                        return rc != JAMD_OK ? rc : O * l->f->d.veclen * l->f->d.splice;
                       });
 }
 
 int jamd_frontend_live_push_host(jamd_frontend_live *l, const int16_t *samples, const int64_t *sample_off,
                                  const unsigned char *final, float *out, int *frame_off) {
-  if (!l || !sample_off) return fe_refuse("jamd_frontend_live_push_host: NULL argument");
+  if (!l || !sample_off) return jamd_refuse("jamd_frontend_live_push_host: NULL argument");
   std::string err;
   long long O = 0;
   for (int c = 0; c < l->nchan; c++) {
     const long long n = fe_span("jamd_frontend_live_push_host", "channel", sample_off, c, err);
-    if (n < 0) return fe_refuse("%s", err.c_str());
+    if (n < 0) return jamd_refuse("%s", err.c_str());
     const bool fin = final && final[c];
     if (n == 0 && !(fin && l->open[c])) continue;
     O += jamd_frontend_live_push_frames(&l->f->d, l->open[c] ? l->ns[c] : 0, n, fin);
   }
   if ((sample_off[l->nchan] > 0 && !samples) || (O > 0 && !out))
-    return fe_refuse("jamd_frontend_live_push_host: NULL buffer");
-  return fe_host_call(&l->stage, l->f->eng, samples, (size_t)sample_off[l->nchan], out, (size_t)O * l->f->d.veclen * l->f->d.splice,
-                      [&](const int16_t *in, float *o, hipStream_t st) {
-                        return jamd_frontend_live_push_dev(l, in, sample_off, final, o, frame_off, st);
+    return jamd_refuse("jamd_frontend_live_push_host: NULL buffer");
+  return jamd_host_call(&l->stage, l->f->eng, samples, (size_t)sample_off[l->nchan], out, (size_t)O * l->f->d.veclen * l->f->d.splice,
+                      [&](const int16_t *in, float *o, hipStream_t st) -> long long {
+                        const int rc = jamd_frontend_live_push_dev(l, in, sample_off, final, o, frame_off, st);
+                        return rc != JAMD_OK ? rc : O * l->f->d.veclen * l->f->d.splice;
                       });
 }
 
 int jamd_frontend_live_commit(jamd_frontend_live *l, const unsigned char *update, void *stream) {
-  if (!l) return fe_refuse("jamd_frontend_live_commit: NULL object");
+  if (!l) return jamd_refuse("jamd_frontend_live_commit: NULL object");
   for (int c = 0; c < l->nchan && l->nopen; c++)
     if (l->open[c] && (!update || update[c])) {
       jamd_set_error("jamd_frontend_live_commit: channel %d has an open segment (end it with a final push first)", c);
@@ -349,17 +332,17 @@ int jamd_frontend_live_commit(jamd_frontend_live *l, const unsigned char *update
 }
 
 int jamd_frontend_cmn_read(const char *path, int veclen, int mfcc_dim, int want_var, float *cmean, float *cvar) {
-  if (!path || !cmean || (want_var && !cvar)) return fe_refuse("jamd_frontend_cmn_read: NULL argument");
+  if (!path || !cmean || (want_var && !cvar)) return jamd_refuse("jamd_frontend_cmn_read: NULL argument");
   std::string err;
   const int r = cmnf_read(path, veclen, mfcc_dim, want_var != 0, cmean, cvar, err);
-  if (r < 0) return fe_refuse("jamd_frontend_cmn_read: %s: %s", path, err.c_str());
+  if (r < 0) return jamd_refuse("jamd_frontend_cmn_read: %s: %s", path, err.c_str());
   return r;
 }
 
 int jamd_frontend_cmn_write(const char *path, int veclen, const float *cmean, const float *cvar) {
-  if (!path || !cmean || veclen < 1) return fe_refuse("jamd_frontend_cmn_write: NULL argument or veclen < 1");
+  if (!path || !cmean || veclen < 1) return jamd_refuse("jamd_frontend_cmn_write: NULL argument or veclen < 1");
   std::string err;
-  if (cmnf_write(path, veclen, cmean, cvar, err) != 0) return fe_refuse("jamd_frontend_cmn_write: %s", err.c_str());
+  if (cmnf_write(path, veclen, cmean, cvar, err) != 0) return jamd_refuse("jamd_frontend_cmn_write: %s", err.c_str());
   return JAMD_OK;
 }
 

@@ -1,7 +1,6 @@
 // gmm_api.hip -- the host layer of GMM scoring: everything of jamd_gmm that is not a kernel or a launcher.
 //
-// jamd_gmm_create() validates the caller's model and packs it into the records the kernels stream
-// (gmm_create_impl), the entry points check their arguments, keep the model's scratch and the utterance
+// jamd_gmm_create() validates the caller's model and packs it into the records the kernels stream, the entry points check their arguments, keep the model's scratch and the utterance
 // boundaries of the running call, and pick the scoring path by what the MODEL is (plain / gprune safe /
 // tied-mixture); which kernel serves a plain call of a given length and vector length is the launcher's
 // business (gmm_outprob.hip).  Nothing is launched from here: see gmm_host.h.
@@ -9,9 +8,7 @@
 
 extern "C" {
 
-// the allocations of jamd_gmm_create(); on any failure the caller releases *gp through jamd_gmm_destroy()
-static int gmm_create_impl(jamd_engine *e, const jamd_gmm_desc *d, int gprune, int gprune_num, jamd_gmm **gp) {
-  jamd_gmm **out = gp;
+int jamd_gmm_create(jamd_engine *e, const jamd_gmm_desc *d, int gprune, int gprune_num, jamd_gmm **out) {
   if (!e || !d || !out) { jamd_set_error("jamd_gmm_create: NULL argument"); return JAMD_EINVAL; }
   *out = nullptr;
   if (d->nstream != 1) {
@@ -42,8 +39,8 @@ static int gmm_create_impl(jamd_engine *e, const jamd_gmm_desc *d, int gprune, i
     return JAMD_EINVAL;
   }
   JAMD_HIP(hipSetDevice(e->device));
-  jamd_gmm *g = new jamd_gmm();
-  *gp = g;                             // owned by the caller from here on
+  std::unique_ptr<jamd_gmm> g(new jamd_gmm());   // (its members own what they hold)
+  int rc;
   g->eng = e; g->S = d->nstate; g->D = d->veclen; g->E = d->nentry;
   g->gprune = gprune; g->gprune_num = gprune_num;
   const int D = g->D;
@@ -110,8 +107,7 @@ static int gmm_create_impl(jamd_engine *e, const jamd_gmm_desc *d, int gprune, i
       }
     }
   }
-  JAMD_HIP(hipMalloc(&g->d_rec, sizeof(float) * (rec.size() ? rec.size() : 4)));
-  JAMD_HIP(hipMemcpy(g->d_rec, rec.data(), sizeof(float) * rec.size(), hipMemcpyHostToDevice));
+  if ((rc = g->d_rec.upload(rec.data(), rec.size())) != JAMD_OK) return rc;
   if (D == 39) {
     // the same records once more in the order K1's record ring loads them (jamd_gmm::d_rec_ring, gmm_host.h): packed
     // here, once per model -- 15.4 MB at 3000 states x 16 mixtures
@@ -125,13 +121,10 @@ static int gmm_create_impl(jamd_engine *e, const jamd_gmm_desc *d, int gprune, i
       for (int c = 1; c < 5; c++)
         for (int k = 0; k < 8; k++) { q[16 * c + k] = r[8 * c - 1 + k]; q[16 * c + 8 + k] = r[D + 8 * c - 1 + k]; }
     }
-    JAMD_HIP(hipMalloc(&g->d_rec_ring, sizeof(float) * (ring.size() ? ring.size() : 4)));
-    JAMD_HIP(hipMemcpy(g->d_rec_ring, ring.data(), sizeof(float) * ring.size(), hipMemcpyHostToDevice));
+    if ((rc = g->d_rec_ring.upload(ring.data(), ring.size())) != JAMD_OK) return rc;
   }
-  JAMD_HIP(hipMalloc(&g->d_st_off, sizeof(int) * (g->S + 1)));
-  JAMD_HIP(hipMemcpy(g->d_st_off, d->st_off, sizeof(int) * (g->S + 1), hipMemcpyHostToDevice));
-  JAMD_HIP(hipMalloc(&g->d_st_off_plain, sizeof(int) * (g->S + 1)));
-  JAMD_HIP(hipMemcpy(g->d_st_off_plain, st_off_plain.data(), sizeof(int) * (g->S + 1), hipMemcpyHostToDevice));
+  if ((rc = g->d_st_off.upload(d->st_off, g->S + 1)) != JAMD_OK) return rc;
+  if ((rc = g->d_st_off_plain.upload(st_off_plain.data(), g->S + 1)) != JAMD_OK) return rc;
   if (g->ntied) {
     // codebooks: the densities of book b in codebook order are the entries of any
     // state tied to it (GCODEBOOK.d[], htk_hmm.h:196-201)
@@ -152,41 +145,20 @@ static int gmm_create_impl(jamd_engine *e, const jamd_gmm_desc *d, int gprune, i
       }
     }
     g->tm_cap = (gprune == JAMD_GPRUNE_NONE) ? g->maxbook : (gprune_num < g->maxbook ? gprune_num : g->maxbook);
-    JAMD_HIP(hipMalloc(&g->d_book_rec, sizeof(float) * (brec.size() ? brec.size() : 4)));
-    JAMD_HIP(hipMemcpy(g->d_book_rec, brec.data(), sizeof(float) * brec.size(), hipMemcpyHostToDevice));
     g->h_book_off = book_off;
-    JAMD_HIP(hipMalloc(&g->d_book_off, sizeof(int) * (g->nbook + 1)));
-    JAMD_HIP(hipMemcpy(g->d_book_off, book_off.data(), sizeof(int) * (g->nbook + 1), hipMemcpyHostToDevice));
-    JAMD_HIP(hipMalloc(&g->d_st_book, sizeof(int) * g->S));
-    JAMD_HIP(hipMemcpy(g->d_st_book, d->st_book, sizeof(int) * g->S, hipMemcpyHostToDevice));
-    JAMD_HIP(hipMalloc(&g->d_ent_logw, sizeof(float) * (g->E ? g->E : 1)));
-    JAMD_HIP(hipMemcpy(g->d_ent_logw, d->ent_logw, sizeof(float) * g->E, hipMemcpyHostToDevice));
-    JAMD_HIP(hipMalloc(&g->d_tied_states, sizeof(int) * g->ntied));
-    JAMD_HIP(hipMemcpy(g->d_tied_states, tied.data(), sizeof(int) * g->ntied, hipMemcpyHostToDevice));
+    if ((rc = g->d_book_rec.upload(brec.data(), brec.size())) != JAMD_OK) return rc;
+    if ((rc = g->d_book_off.upload(book_off.data(), g->nbook + 1)) != JAMD_OK) return rc;
+    if ((rc = g->d_st_book.upload(d->st_book, g->S)) != JAMD_OK) return rc;
+    if ((rc = g->d_ent_logw.upload(d->ent_logw, g->E)) != JAMD_OK) return rc;
+    if ((rc = g->d_tied_states.upload(tied.data(), g->ntied)) != JAMD_OK) return rc;
   }
-  return JAMD_OK;
-}
-
-
-int jamd_gmm_create(jamd_engine *e, const jamd_gmm_desc *d, int gprune, int gprune_num,
-                    jamd_gmm **out) {
-  if (!e || !d || !out) { jamd_set_error("jamd_gmm_create: NULL argument"); return JAMD_EINVAL; }
-  *out = nullptr;
-  jamd_gmm *g = nullptr;
-  const int rc = gmm_create_impl(e, d, gprune, gprune_num, &g);
-  if (rc != JAMD_OK) { if (g) jamd_gmm_destroy(g); return rc; }   // no leak on a failed allocation or a bad descriptor
-  *out = g;
+  *out = g.release();
   return JAMD_OK;
 }
 
 void jamd_gmm_destroy(jamd_gmm *g) {
   if (!g) return;
   (void)hipSetDevice(g->eng->device);
-  void *ptrs[] = { g->d_rec, g->d_rec_ring, g->d_cur_utt_off, g->d_st_off, g->d_st_off_plain, g->d_tied_states, g->d_st_book, g->d_book_off, g->d_book_rec,
-                   g->d_ent_logw, g->d_frames, g->d_out, g->d_tm_score, g->d_tm_id, g->d_tm_num, g->d_tm_flag, g->d_narrow };
-  for (void *p : ptrs) if (p) (void)hipFree(p);
-  if (g->h_utt_off) (void)hipHostFree(g->h_utt_off);
-  if (g->ev_utt_off) (void)hipEventDestroy(g->ev_utt_off);
   delete g;
 }
 
@@ -232,45 +204,27 @@ int jamd_gmm_dens_host(jamd_gmm *g, const float *host_frames, int T, float *host
   if (!g || !host_frames || !host_out || T < 0) { jamd_set_error("jamd_gmm_dens_host: bad argument"); return JAMD_EINVAL; }
   if (T == 0) return JAMD_OK;
   JAMD_HIP(hipSetDevice(g->eng->device));
-  float *d_fr = nullptr, *d_out = nullptr;
-  int rc = JAMD_OK;
-  hipStream_t st = g->eng->stream;
   const int E = jamd_gmm_nentry(g);
   if (E <= 0) { jamd_set_error("jamd_gmm_dens_host: no single column order for this model"); return JAMD_EINVAL; }
-  if (hipMalloc(&d_fr, sizeof(float) * (size_t)T * g->D) != hipSuccess ||
-      hipMalloc(&d_out, sizeof(float) * (size_t)T * E) != hipSuccess) {
-    jamd_set_error("jamd_gmm_dens_host: out of device memory"); rc = JAMD_ENOMEM;
-  }
-  if (rc == JAMD_OK && hipMemcpyAsync(d_fr, host_frames, sizeof(float) * (size_t)T * g->D, hipMemcpyHostToDevice, st) != hipSuccess) rc = JAMD_ENODEV;
-  if (rc == JAMD_OK) rc = jamd_gmm_dens_dev(g, d_fr, T, d_out, st);
-  if (rc == JAMD_OK && (hipMemcpyAsync(host_out, d_out, sizeof(float) * (size_t)T * E, hipMemcpyDeviceToHost, st) != hipSuccess ||
-                        hipStreamSynchronize(st) != hipSuccess)) { jamd_set_error("jamd_gmm_dens_host: copy failed"); rc = JAMD_ELAUNCH; }
-  if (d_fr) (void)hipFree(d_fr);
-  if (d_out) (void)hipFree(d_out);
-  return rc;
+  return jamd_host_call(&g->dens_stage, g->eng, host_frames, (size_t)T * g->D, host_out, (size_t)T * E,
+                        [&](const float *in, float *o, hipStream_t st) -> long long {
+                          const int rc = jamd_gmm_dens_dev(g, in, T, o, st);
+                          return rc != JAMD_OK ? rc : (long long)T * E;
+                        }, JAMD_ELAUNCH);
 }
 
 // utterance boundaries of the running call, for the one scoring path that cares where an input begins
 static int set_utterances(jamd_gmm *g, const int *utt_off, int nutt, hipStream_t st) {
   if (g->ntied == 0 || g->gprune == JAMD_GPRUNE_NONE) return JAMD_OK;   // (heu / beam arrive here as safe + hist_method)
-  int rc;
-  if ((rc = jamd_grow(&g->d_cur_utt_off, &g->utt_off_bytes, sizeof(int) * ((size_t)nutt + 1))) != JAMD_OK) return rc;
   // utt_off is the caller's memory: staged in a PINNED buffer the model owns, so that the copy is truly asynchronous (a
   // pipelining host keeps its scoring stream free of host waits; from pageable memory the runtime would either block or
-  // stage).  An event behind the copy guards the buffer: the next call on this model waits for it before it rewrites the
-  // staging copy (normally long done) -- d_cur_utt_off itself is ordered by the stream.
-  if (g->ev_utt_off) JAMD_HIP(hipEventSynchronize(g->ev_utt_off));
-  else JAMD_HIP(hipEventCreateWithFlags(&g->ev_utt_off, hipEventDisableTiming));
-  if ((size_t)(nutt + 1) > g->h_utt_off_cap) {
-    if (g->h_utt_off) JAMD_HIP(hipHostFree(g->h_utt_off));
-    g->h_utt_off = nullptr; g->h_utt_off_cap = 0;
-    const size_t cap = (size_t)nutt + 1 < 1024 ? 1024 : (size_t)nutt + 1;
-    JAMD_HIP(hipHostMalloc((void **)&g->h_utt_off, sizeof(int) * cap, hipHostMallocDefault));
-    g->h_utt_off_cap = cap;
-  }
-  memcpy(g->h_utt_off, utt_off, sizeof(int) * ((size_t)nutt + 1));
-  JAMD_HIP(hipMemcpyAsync(g->d_cur_utt_off, g->h_utt_off, sizeof(int) * ((size_t)nutt + 1), hipMemcpyHostToDevice, st));
-  JAMD_HIP(hipEventRecord(g->ev_utt_off, st));
+  // stage).  The next call on this model waits for the copy before it rewrites the staging buffer (normally long done);
+  // utt.d itself is ordered by the stream.
+  const size_t bytes = sizeof(int) * ((size_t)nutt + 1);
+  int rc;
+  if ((rc = g->utt.begin(bytes < 4096 ? 4096 : bytes)) != JAMD_OK) return rc;
+  memcpy(g->utt.h.p, utt_off, bytes);
+  if ((rc = g->utt.send(bytes, st)) != JAMD_OK) return rc;
   g->cur_nutt = nutt;
   return JAMD_OK;
 }
@@ -307,9 +261,9 @@ int jamd_gmm_outprob_utts_dev(jamd_gmm *g, const float *dev_frames, const int *u
   if (g->ntied) {
     // calc_tied_mix(): codebook top-N cache per (frame, book), then the states
     const size_t n = (size_t)T * g->nbook * g->tm_cap;
-    if ((rc = jamd_grow(&g->d_tm_score, &g->tm_cap_bytes, sizeof(float) * n)) != JAMD_OK) return rc;
-    if ((rc = jamd_grow(&g->d_tm_id, &g->tm_id_bytes, sizeof(int) * n)) != JAMD_OK) return rc;
-    if ((rc = jamd_grow(&g->d_tm_num, &g->tm_num_bytes, sizeof(int) * (size_t)T * g->nbook)) != JAMD_OK) return rc;
+    if ((rc = g->d_tm_score.grow(sizeof(float) * n)) != JAMD_OK) return rc;
+    if ((rc = g->d_tm_id.grow(sizeof(int) * n)) != JAMD_OK) return rc;
+    if ((rc = g->d_tm_num.grow(sizeof(int) * (size_t)T * g->nbook)) != JAMD_OK) return rc;
     if ((rc = jamd_gmm_launch_tmix(g, dev_frames, T, dev_out, g->d_tm_score, g->d_tm_id, g->d_tm_num, st)) != JAMD_OK) return rc;
   }
   hipError_t le = hipGetLastError();
@@ -326,22 +280,11 @@ int jamd_gmm_outprob_host(jamd_gmm *g, const float *host_frames, int T, float *h
     return JAMD_EINVAL;
   }
   if (T == 0) return JAMD_OK;
-  JAMD_HIP(hipSetDevice(g->eng->device));
-  int rc;
-  if ((rc = jamd_grow(&g->d_frames, &g->frames_cap, sizeof(float) * (size_t)T * g->D)) != JAMD_OK) return rc;
-  if ((rc = jamd_grow(&g->d_out, &g->out_cap, sizeof(float) * (size_t)T * g->S)) != JAMD_OK) return rc;
-  hipStream_t st = g->eng->stream;
-  JAMD_HIP(hipMemcpyAsync(g->d_frames, host_frames, sizeof(float) * (size_t)T * g->D,
-                          hipMemcpyHostToDevice, st));
-  if ((rc = jamd_gmm_outprob_dev(g, g->d_frames, T, g->d_out, st)) != JAMD_OK) return rc;
-  JAMD_HIP(hipMemcpyAsync(host_out, g->d_out, sizeof(float) * (size_t)T * g->S,
-                          hipMemcpyDeviceToHost, st));
-  hipError_t se = hipStreamSynchronize(st);
-  if (se != hipSuccess) {
-    jamd_set_error("jamd_gmm_outprob_host: execution failed: %s", hipGetErrorString(se));
-    return JAMD_ELAUNCH;
-  }
-  return JAMD_OK;
+  return jamd_host_call(&g->stage, g->eng, host_frames, (size_t)T * g->D, host_out, (size_t)T * g->S,
+                        [&](const float *in, float *o, hipStream_t st) -> long long {
+                          const int rc = jamd_gmm_outprob_dev(g, in, T, o, st);
+                          return rc != JAMD_OK ? rc : (long long)T * g->S;
+                        }, JAMD_ELAUNCH);
 }
 
 int jamd_gmm_tmix_cap(const jamd_gmm *g) { return g ? g->tm_cap : -1; }

@@ -486,7 +486,7 @@ gmm_narrow_lse_kernel(const float *__restrict__ dens, const int *__restrict__ st
 template <int D>
 int launch_narrow(jamd_gmm *g, const float *frames, int T, float *out, hipStream_t st) {
   const int E = g->E_plain;
-  int rc = jamd_grow(&g->d_narrow, &g->narrow_cap, sizeof(float) * (size_t)kNarrowT * (size_t)E);   // (first narrow call only)
+  int rc = g->d_narrow.grow(sizeof(float) * (size_t)kNarrowT * (size_t)E);   // (first narrow call only)
   if (rc != JAMD_OK) return rc;
   const int grid = (E + 63) / 64;
   const int nfb = (T + kNarrowFB - 1) / kNarrowFB;

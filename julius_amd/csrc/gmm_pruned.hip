@@ -435,10 +435,10 @@ int launch_book_hist(jamd_gmm *g, const float *frames, float *c_score, int *c_id
   if (rc != JAMD_OK) return rc;
   if (g->hist_method == JAMD_GPRUNE_BEAM)
     hipLaunchKernelGGL(tmix_book_hist_kernel<JAMD_GPRUNE_BEAM>, grid, dim3(64), dyn, st, g->d_book_rec, g->d_book_off, frames,
-                       g->d_cur_utt_off, c_score, c_id, c_num, g->nbook, g->D, g->rec, g->tm_cap, g->maxbook);
+                       (const int *)g->utt.d.p, c_score, c_id, c_num, g->nbook, g->D, g->rec, g->tm_cap, g->maxbook);
   else
     hipLaunchKernelGGL(tmix_book_hist_kernel<JAMD_GPRUNE_HEU>, grid, dim3(64), dyn, st, g->d_book_rec, g->d_book_off, frames,
-                       g->d_cur_utt_off, c_score, c_id, c_num, g->nbook, g->D, g->rec, g->tm_cap, g->maxbook);
+                       (const int *)g->utt.d.p, c_score, c_id, c_num, g->nbook, g->D, g->rec, g->tm_cap, g->maxbook);
   return JAMD_OK;
 }
 
@@ -458,14 +458,14 @@ int launch_book(jamd_gmm *g, const float *frames, int T, float *c_score, int *c_
     return JAMD_OK;
   };
   if (g->gprune == JAMD_GPRUNE_NONE) return launch(std::integral_constant<int, 0>{});
-  int rc = jamd_grow(&g->d_tm_flag, &g->tm_flag_bytes, sizeof(int) * (size_t)T * g->nbook);
+  int rc = g->d_tm_flag.grow(sizeof(int) * (size_t)T * g->nbook);
   if (rc != JAMD_OK) return rc;
   if ((rc = dispatch_topn<2>(cap, launch)) != JAMD_OK) return rc;
   // ... and the marked frames again in the reference's visiting order
   const size_t odyn = sizeof(float) * (size_t)g->D + sizeof(int) * (size_t)g->maxbook;
   if ((rc = jamd_reserve_dyn_lds((const void *)tmix_book_safe_order_kernel, odyn, "gprune safe over tied-mixture codebooks")) != JAMD_OK) return rc;
   hipLaunchKernelGGL(tmix_book_safe_order_kernel, dim3(g->nbook, g->cur_nutt < 65535 ? g->cur_nutt : 65535), dim3(64), odyn, st,
-                     g->d_book_rec, g->d_book_off, frames, g->d_cur_utt_off, g->d_tm_flag, c_score, c_id, c_num, g->cur_nutt,
+                     g->d_book_rec, g->d_book_off, frames, (const int *)g->utt.d.p, g->d_tm_flag, c_score, c_id, c_num, g->cur_nutt,
                      g->nbook, g->D, g->rec, cap);
   return JAMD_OK;
 }

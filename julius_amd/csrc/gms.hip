@@ -1,4 +1,5 @@
-// gms.hip -- Gaussian mixture selection (-gshmm / -gsnum) on gfx950.
+// gms.hip -- Gaussian mixture selection (-gshmm / -gsnum) on gfx950: the kernels and their launcher; the C ABI of
+// jamd_gms is in gms_api.hip (gms_host.h).
 //
 // Replaces gms_state() and its helpers (libsent/src/phmm/gms.c:189-412, gms_gprune.c:80-257):
 // with a selection model loaded, Julius scores a small monophone GMM set ("GS HMM") every frame,
@@ -19,18 +20,7 @@
 // heap in LDS.  Even then the index array is reset at every utterance (the reference never resets
 // it), which again can only matter for an exact tie on the boundary.
 #include "jamd_device.h"
-
-struct jamd_gms {
-  jamd_engine *eng = nullptr;
-  jamd_gmm *gs = nullptr;          // the selection model (per-Gaussian scores)
-  int Sgs = 0, Egs = 0, S = 0, nbest = 0, strict = 0;
-  int *d_st_off = nullptr;         // [Sgs + 1]
-  float *d_logw = nullptr;         // [Egs]
-  int *d_state2gs = nullptr;       // [S]
-  int *d_utt_off = nullptr; size_t utt_bytes = 0;
-  float *d_dens = nullptr; size_t dens_cap = 0;
-  float *d_fs = nullptr; size_t fs_cap = 0;
-};
+#include "gms_host.h"
 
 namespace {
 using namespace jamd;
@@ -174,103 +164,15 @@ gms_combine_kernel(const float *__restrict__ fs, const int *__restrict__ state2g
 
 }  // namespace
 
-extern "C" {
-
-int jamd_gms_create(jamd_engine *e, const jamd_gmm_desc *gs, const int *state2gs, int nstate, int nbest,
-                    jamd_gms **out) {
-  if (!e || !gs || !state2gs || !out || nstate <= 0 || nbest < 1) { jamd_set_error("jamd_gms_create: bad argument"); return JAMD_EINVAL; }
-  *out = nullptr;
-  if (gs->nbook > 0 || gs->nstream != 1) { jamd_set_error("jamd_gms_create: the selection model must be a plain single-stream GMM"); return JAMD_EINVAL; }
-  for (int s = 0; s < nstate; s++)
-    if (state2gs[s] >= gs->nstate) { jamd_set_error("jamd_gms_create: state2gs[%d] out of range", s); return JAMD_EINVAL; }
-  // compute_g_max() starts from a state's last entry: the reference's reader cannot produce a state without one
-  for (int i = 0; gs->st_off && i < gs->nstate; i++)
-    if (gs->st_off[i + 1] - gs->st_off[i] < 1) { jamd_set_error("jamd_gms_create: selection state %d has no Gaussians", i); return JAMD_EINVAL; }
-  JAMD_HIP(hipSetDevice(e->device));
-  jamd_gms *m = new jamd_gms();
-  m->eng = e; m->Sgs = gs->nstate; m->Egs = gs->nentry; m->S = nstate; m->nbest = nbest;
-  int rc = jamd_gmm_create(e, gs, JAMD_GPRUNE_NONE, 0, &m->gs);
-  if (rc == JAMD_OK && hipMalloc(&m->d_st_off, sizeof(int) * (gs->nstate + 1)) != hipSuccess) rc = JAMD_ENOMEM;
-  if (rc == JAMD_OK && hipMalloc(&m->d_logw, sizeof(float) * (gs->nentry > 0 ? gs->nentry : 1)) != hipSuccess) rc = JAMD_ENOMEM;
-  if (rc == JAMD_OK && hipMalloc(&m->d_state2gs, sizeof(int) * nstate) != hipSuccess) rc = JAMD_ENOMEM;
-  if (rc == JAMD_OK &&
-      (hipMemcpy(m->d_st_off, gs->st_off, sizeof(int) * (gs->nstate + 1), hipMemcpyHostToDevice) != hipSuccess ||
-       hipMemcpy(m->d_logw, gs->ent_logw, sizeof(float) * gs->nentry, hipMemcpyHostToDevice) != hipSuccess ||
-       hipMemcpy(m->d_state2gs, state2gs, sizeof(int) * nstate, hipMemcpyHostToDevice) != hipSuccess)) rc = JAMD_ENODEV;
-  if (rc != JAMD_OK) { if (rc == JAMD_ENOMEM) jamd_set_error("jamd_gms_create: out of device memory"); jamd_gms_destroy(m); return rc; }
-  *out = m;
-  return JAMD_OK;
-}
-
-int jamd_gms_nstate(const jamd_gms *m) { return m ? m->S : 0; }
-
-int jamd_gms_set_strict_order(jamd_gms *m, int on) {
-  if (!m) { jamd_set_error("jamd_gms_set_strict_order: NULL"); return JAMD_EINVAL; }
-  m->strict = on != 0;
-  return JAMD_OK;
-}
-
-void jamd_gms_destroy(jamd_gms *m) {
-  if (!m) return;
-  (void)hipSetDevice(m->eng->device);
-  if (m->gs) jamd_gmm_destroy(m->gs);
-  void *ptrs[] = { m->d_st_off, m->d_logw, m->d_state2gs, m->d_utt_off, m->d_dens, m->d_fs };
-  for (void *p : ptrs) if (p) (void)hipFree(p);
-  delete m;
-}
-
-int jamd_gms_apply_dev(jamd_gms *m, const float *dev_frames, int T, const int *utt_off, int nutt,
-                       float *dev_scores, void *stream) {
-  if (!m || !dev_frames || !dev_scores || T < 0 || (utt_off && nutt < 1)) { jamd_set_error("jamd_gms_apply_dev: bad argument"); return JAMD_EINVAL; }
-  if (T == 0) return JAMD_OK;
-  JAMD_HIP(hipSetDevice(m->eng->device));
-  hipStream_t st = jamd_stream(m->eng, stream);
-  const int one[2] = {0, T};
-  if (!utt_off) { utt_off = one; nutt = 1; }
-  if (utt_off[0] != 0 || utt_off[nutt] != T) { jamd_set_error("jamd_gms_apply_dev: utt_off must run from 0 to T"); return JAMD_EINVAL; }
-  int rc;
-  if ((rc = jamd_grow(&m->d_utt_off, &m->utt_bytes, sizeof(int) * ((size_t)nutt + 1))) != JAMD_OK) return rc;
-  if ((rc = jamd_grow(&m->d_dens, &m->dens_cap, sizeof(float) * ((size_t)T * m->Egs + 64))) != JAMD_OK) return rc;
-  if ((rc = jamd_grow(&m->d_fs, &m->fs_cap, sizeof(float) * (size_t)T * m->Sgs)) != JAMD_OK) return rc;
-  JAMD_HIP(hipMemcpyAsync(m->d_utt_off, utt_off, sizeof(int) * (nutt + 1), hipMemcpyHostToDevice, st));
-  if ((rc = jamd_gmm_dens_dev(m->gs, dev_frames, T, m->d_dens, st)) != JAMD_OK) return rc;
-  const int EgsPad = (m->Egs + 63) & ~63;
-  const size_t lds = sizeof(float) * ((size_t)3 * m->Sgs + m->Sgs + 1 + m->Egs + 64 + 2 * (size_t)EgsPad);
-  if (lds > 159 * 1024) { jamd_set_error("jamd_gms_apply_dev: a selection model of %d states / %d Gaussians does not fit in LDS", m->Sgs, m->Egs); return JAMD_EINVAL; }
+// ---- launcher (gms_host.h)
+int gms_launch(jamd_gms *m, hipStream_t st, int T, int nutt, float *dev_scores) {
+  const int EgsPad = gms_egs_pad(m->Egs);
+  const size_t lds = gms_lds_bytes(m->Sgs, m->Egs);
   auto kern = m->strict ? gms_select_kernel<true> : gms_select_kernel<false>;
   if (lds > 48 * 1024) JAMD_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   hipLaunchKernelGGL(kern, dim3(nutt), dim3(64), lds, st, m->d_dens, m->d_st_off, m->d_logw, m->d_utt_off,
                      m->d_fs, m->Sgs, m->Egs, EgsPad, m->nbest);
   hipLaunchKernelGGL(gms_combine_kernel, dim3((m->S + 255) / 256, T < 1024 ? T : 1024), dim3(256), 0, st, m->d_fs,
                      m->d_state2gs, dev_scores, T, m->S, m->Sgs);
-  hipError_t le = hipGetLastError();
-  if (le != hipSuccess) { jamd_set_error("jamd_gms_apply_dev: launch failed: %s", hipGetErrorString(le)); return JAMD_ELAUNCH; }
   return JAMD_OK;
 }
-
-int jamd_gms_apply_host(jamd_gms *m, const float *host_frames, int T, const int *utt_off, int nutt,
-                        float *host_scores) {
-  if (!m || !host_frames || !host_scores || T < 0) { jamd_set_error("jamd_gms_apply_host: bad argument"); return JAMD_EINVAL; }
-  if (T == 0) return JAMD_OK;
-  JAMD_HIP(hipSetDevice(m->eng->device));
-  hipStream_t st = m->eng->stream;
-  const int D = jamd_gmm_veclen(m->gs);
-  float *d_fr = nullptr, *d_sc = nullptr;
-  int rc = JAMD_OK;
-  if (hipMalloc(&d_fr, sizeof(float) * (size_t)T * D) != hipSuccess ||
-      hipMalloc(&d_sc, sizeof(float) * (size_t)T * m->S) != hipSuccess) {
-    jamd_set_error("jamd_gms_apply_host: out of device memory"); rc = JAMD_ENOMEM;
-  }
-  if (rc == JAMD_OK && (hipMemcpyAsync(d_fr, host_frames, sizeof(float) * (size_t)T * D, hipMemcpyHostToDevice, st) != hipSuccess ||
-                        hipMemcpyAsync(d_sc, host_scores, sizeof(float) * (size_t)T * m->S, hipMemcpyHostToDevice, st) != hipSuccess)) {
-    jamd_set_error("jamd_gms_apply_host: copy failed"); rc = JAMD_ENODEV;
-  }
-  if (rc == JAMD_OK) rc = jamd_gms_apply_dev(m, d_fr, T, utt_off, nutt, d_sc, st);
-  if (rc == JAMD_OK && (hipMemcpyAsync(host_scores, d_sc, sizeof(float) * (size_t)T * m->S, hipMemcpyDeviceToHost, st) != hipSuccess ||
-                        hipStreamSynchronize(st) != hipSuccess)) { jamd_set_error("jamd_gms_apply_host: copy failed"); rc = JAMD_ELAUNCH; }
-  if (d_fr) (void)hipFree(d_fr);
-  if (d_sc) (void)hipFree(d_sc);
-  return rc;
-}
-
-}  // extern "C"

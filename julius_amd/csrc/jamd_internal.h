@@ -41,17 +41,6 @@ struct jamd_engine {
   int num_cu = 256;
 };
 
-// Grows the device buffer *p to at least `bytes` (its contents are not kept); *cap is the size it has.
-template <typename T>
-static inline int jamd_grow(T **p, size_t *cap, size_t bytes) {
-  if (*cap >= bytes) return JAMD_OK;
-  if (*p) JAMD_HIP(hipFree(*p));
-  *p = nullptr; *cap = 0;
-  JAMD_HIP(hipMalloc((void **)p, bytes));
-  *cap = bytes;
-  return JAMD_OK;
-}
-
 // A kernel whose static + dynamic LDS passes the default 64 KB window needs the attribute raised, and the sum
 // must fit the 160 KB of a CU (the generic-D kernels keep 2 KB of frame data per vector component in LDS).
 static inline int jamd_reserve_dyn_lds(const void *kernel, size_t dyn, const char *what) {
