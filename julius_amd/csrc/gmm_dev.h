@@ -10,18 +10,38 @@ typedef float f2 __attribute__((ext_vector_type(2)));
 
 namespace jamd {
 
-// XCD-aware block decode: the dispatcher places block b on XCD b % 8
-// (MI355X_MICROARCH.md "Workgroup dispatch"); all frame-blocks of one state
-// range are given the same b % 8 so the range's records stay in that XCD's L2.
+// XCD-aware block decode: the dispatcher places block b on XCD b % 8 (MI355X_MICROARCH.md "Workgroup dispatch").
+// With nstb = 8 k + r state ranges:
+//   * the first 8 k ranges (the full rounds) are pinned to one XCD each -- all frame-blocks of a range are given the
+//     same b % 8, frame block fastest -- so the range's records stay in that XCD's L2;
+//   * the r leftover ranges hold L = r * nfb blocks, and those are dealt over ALL eight XCDs in equal shares: XCD x takes
+//     the contiguous run m = x * per .. x * per + per - 1 (per = ceil(L / 8)) of the leftover blocks counted range by
+//     range, frame block fastest.  per <= nfb, so a run touches at most two ranges: an XCD's L2 takes in the records
+//     of at most two leftover ranges (a range's records land in about 8 / r + 1 L2s instead of one -- 82 KB each at
+//     M = 16, D = 39).  Pinned like the full rounds, r of the XCDs would carry nfb blocks more than the others and
+//     the launch would end with 8 - r XCDs idle for a whole block's time ("launch shape").  The price
+//     is paid where the whole launch is one round and per is 1 or 2: nothing to save there, and a block that reads
+//     its range alone in its XCD is slower than two that share it (a 1 000-frame call + 1 %).
+// The grid is 8 k nfb + 8 per blocks (the first term a multiple of 8, so a leftover block's b % 8 is its share's
+// number); the at most 7 blocks with m >= L are empty.
 __device__ __forceinline__ bool decode_block(int nfb, int nstb, int &fb, int &sb) {
   const int b = blockIdx.x;
-  const int xcd = b & 7, q = b >> 3;
-  sb = xcd + 8 * (q / nfb);
-  fb = q % nfb;
-  return sb < nstb;
+  const int x = b & 7;
+  const int kfull = nstb & ~7, full = kfull * nfb;      // ranges and blocks of the full rounds
+  const bool tail = b >= full;
+  const int L = (nstb - kfull) * nfb, per = (L + 7) >> 3;
+  const int n = tail ? x * per + ((b - full) >> 3) : b >> 3;
+  if (tail && n >= L) return false;
+  const int d = n / nfb;
+  sb = tail ? kfull + d : x + 8 * d;
+  fb = n - d * nfb;
+  return true;
 }
-// ... and the grid it decodes: nfb frame-blocks for each of nstb ranges, the ranges rounded up to whole rounds of 8 XCDs
-static inline int xcd_grid(int nstb, int nfb) { return 8 * ((nstb + 7) / 8) * nfb; }
+// ... and the grid it decodes: nfb frame-blocks for each of nstb ranges, the leftover blocks rounded up to a multiple of 8
+static inline int xcd_grid(int nstb, int nfb) {
+  const int kfull = nstb & ~7;
+  return kfull * nfb + 8 * (((nstb - kfull) * nfb + 7) / 8);
+}
 
 // The vector lengths the kernels are compiled for: f(std::integral_constant<int, DT>) with DT = D for those, DT = 0
 // (run-time dimension, frames in LDS) for every other.

@@ -360,10 +360,12 @@ int launch_tile(jamd_gmm *g, const float *frames, int T, float *out, hipStream_t
   // States per block: NS, the width of the output tile -- the smallest there is.  A block's fixed cost (its 128
   // frames per wave loaded into registers) is nothing against 16 states x 16 Gaussians of arithmetic, and short
   // blocks are what keeps the last wave of blocks of a launch short: at 64 000 frames a launch is four rounds of
-  // 96-state blocks or twenty-three rounds of 16-state ones, 10.97 vs 9.93 ms (sweep on MI355X: 16 / 32 / 48 / 64 /
-  // 96 / 128 states -> 9.93 / 10.02 / 10.35 / 10.62 / 10.97 / 11.22 ms; 384 000 frames: 60.4 vs 61.8 ms; 16 000:
-  // 2.63 vs 2.78 ms).  Block b runs on XCD b % 8 and a state range is pinned to one XCD (decode_block), so the
-  // blocks that share a range share an L2.
+  // 96-state blocks or twenty-three rounds of 16-state ones (23 500 blocks over 1 024 block slots: 22.95; the sweep
+  // below was taken when the deal still left four XCDs a twenty-fourth), 10.97 vs 9.93 ms (sweep on MI355X: 16 / 32 /
+  // 48 / 64 / 96 / 128 states -> 9.93 / 10.02 / 10.35 / 10.62 / 10.97 / 11.22 ms; 384 000 frames: 60.4 vs 61.8 ms;
+  // 16 000: 2.63 vs 2.78 ms).  Block b runs on XCD b % 8; a state range of the full rounds of eight is pinned to one
+  // XCD, so the blocks that share it share an L2, and the blocks of the leftover ranges (188 = 8 x 23 + 4 at 3 000
+  // states) are dealt evenly over all eight (decode_block).
   const int nsb = NS;
   const int nstb = (g->S + nsb - 1) / nsb;
   const int grid = xcd_grid(nstb, nfb);
@@ -428,7 +430,8 @@ gmm_narrow_dens_kernel(const float *__restrict__ rec, const float *__restrict__ 
                        int nfb, int neb) {
   constexpr int REC = (2 * D + 2 + 3) & ~3;
   // the frame blocks of one range of 64 entries run on ONE XCD (block b is placed on XCD b % 8): the range's records
-  // come from HBM / Infinity Cache once and from that XCD's L2 for the other frame blocks (decode_block(), as K1)
+  // come from HBM / Infinity Cache once and from that XCD's L2 for the other frame blocks; the ranges left over from
+  // whole rounds of eight are spread over all XCDs, each on at most two (decode_block(), as K1)
   int fbk, ebk;
   if (!decode_block(nfb, neb, fbk, ebk)) return;
   const int e = ebk * 64 + threadIdx.x;

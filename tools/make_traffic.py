@@ -2,6 +2,8 @@
 """profiles/traffic_gmm_tile.json and profiles/traffic_first_pass.json from the PMC summaries of tools/r05_profiles.sh
 (gpurun_out/<round>/*_traffic_pmc_summary.json: rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE in separate runs).
 
+    tools/make_traffic.py [round [gmm]]       # `gmm`: K1's file alone (the first-pass summaries need not be there)
+
 Units and corrections (MI355X_MICROARCH.md "HBM"): both counters are in KiB-sized units of 1024 B as rocprofv3 reports them
 (FETCH_SIZE = TCC_EA0_RDREQ x 64 B / 1024), memory-side of the L2, Infinity-Cache hits included.  On gfx950 FETCH_SIZE
 reports half of the bytes of WIDE COALESCED reads (128-B requests tallied at 64 B): K1's reads are of that kind (frames and
@@ -34,16 +36,18 @@ def counters(name, sub):
 
 g = counters("gmm", "gmm_tile")
 fetch, write = g["FETCH_SIZE"] * 1024.0, g["WRITE_SIZE"] * 1024.0
-gm = {"kernel": "gmm_tile<D=39,FPL=2,NS=16> grid=24000 nsb=16", "rocprof_kernel_name": g["rocprof_kernel_name"],
+gm = {"kernel": "gmm_tile<D=39,FPL=2,NS=16,ring> grid=23504 nsb=16", "rocprof_kernel_name": g["rocprof_kernel_name"],
       "frames_per_launch": 64000,
       "source": f"profiles/{rnd}_gmm_traffic_pmc_summary.json (rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE, separate passes, bench.py --workload gmm "
-                "--steps 3 --warmup 1 --no-cpu-baseline: 64 utterances x 1000 frames per launch), the kernel of round 5 (log-sum step of 22 "
-                "instructions; the tiling, and so the traffic, is round 4's); 'kernel' is the string gmm.last_kernel() reports, which bench.py requires to match",
+                "--steps 3 --warmup 1 --no-cpu-baseline --no-small-T: 64 utterances x 1000 frames per launch), the record-ring kernel with the "
+                "leftover state ranges dealt over all XCDs (23 504 blocks); 'kernel' is the string gmm.last_kernel() reports, which bench.py requires to match",
       "FETCH_SIZE_KB_avg_per_dispatch": g["FETCH_SIZE"], "WRITE_SIZE_KB_avg_per_dispatch": g["WRITE_SIZE"],
       "correction": "MI355X_MICROARCH.md 'HBM': on gfx950 FETCH_SIZE tallies 128-B requests at 64 B -> doubled (wide coalesced reads); WRITE_SIZE as reported (the [T][S] output is 768.0 MB)",
       "hbm_bytes_per_launch": int(2 * fetch + write), "kernel_ms_under_pmc": g.get("avg_ms")}
 (ROOT / "profiles" / "traffic_gmm_tile.json").write_text(json.dumps(gm, indent=1))
 print("gmm", gm["hbm_bytes_per_launch"])
+if sys.argv[2:3] == ["gmm"]:
+    sys.exit(0)
 
 entries = []
 for name, sub, dnn, mp, utts, beam, shape, frames in (
