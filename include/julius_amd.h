@@ -948,7 +948,8 @@ int  jamd_adin_state_get(jamd_adin *a, int chan, int *zlen, float *zmean, int64_
  * per channel the last max(c_length, sbsize) + chunk_size samples (with their running crossing count) and copies
  * ranges; cbuf / swapbuf have no copies.  Per channel it also keeps is_valid_data, nc, rest_tail, sblen, the trigger
  * state of count_zc_e() and the samples of an incomplete block.
- * NOT SERVED: -fvad; -rejectshort / -powerthres; segmentation asked for by the recogniser (ad_process() returning 1) or
+ * -fvad / -fvad_param (the libfvad detector gating the trigger) is jamd_adin_cut_create_fvad(), further below.
+ * NOT SERVED: -rejectshort / -powerthres; segmentation asked for by the recogniser (ad_process() returning 1) or
  * by MAXSPEECHLEN; last_trigger_len beyond part_start; audio files in jamd_batch.  Descriptors with which the reference
  * overruns its swap buffer are refused (jamd_adin_cut_params()). */
 typedef struct {
@@ -1010,6 +1011,110 @@ int  jamd_adin_cut_push_host(jamd_adin_cut *k, const int16_t *samples, const int
  * reset.  Any pointer may be NULL. */
 int  jamd_adin_cut_state_get(jamd_adin_cut *k, int chan, int *is_valid, int *nc, int *rest_tail, int *sblen,
                              int *zero_cross, int *carried, int64_t *stream_pos);
+
+/* ---- the voice-activity detector behind -fvad: libfvad (WebRTC VAD) on 10 ms frames, many channels per call ----
+ * What fvad_process() (libjulius/libfvad) returns for each 10 ms frame of a channel's stream, before it is clamped to
+ * 0 / 1: the core's raw value, 0 for noise, 1 for speech, 2 + the hangover left for a noise frame inside the hangover.
+ * 16-bit and 32-bit integer arithmetic throughout, bit for bit the reference's, its wrap-arounds on saturated input
+ * included.  At 16 kHz a two-branch all-pass halves the rate; five all-pass split filters and a high-pass make six
+ * bands; each band gives a log energy; two Gaussians per band for noise and for speech decide, and the decision says
+ * which of the two models adapts.  The filter states, the adapted models, the minimum tracker and the hangover are kept
+ * per channel on the device, with the samples of an incomplete frame.
+ * Every array constant of the reference comes from the caller (as the FIR tables of -48 do): jamd_fvad_model, filled
+ * from a file that julius_amd/shim/jamd_fvad_export writes out of the user's Julius tree.
+ * NOT SERVED: 32000 and 48000 Hz input (valid in libfvad); frames of 20 and 30 ms (Julius uses 10 ms). */
+typedef struct {
+  int allpass_q15[2];            /* vad_filterbank.c kAllPassCoefsQ15: the split filters' two branches      */
+  int allpass_q13[2];            /* vad_sp.c         kAllPassCoefsQ13: the 16 -> 8 kHz stage                */
+  int hp_zero[3];                /* vad_filterbank.c kHpZeroCoefs                                           */
+  int hp_pole[3];                /*                  kHpPoleCoefs                                           */
+  int offset[6];                 /*                  kOffsetVector, per band                                */
+  int spectrum_weight[6];        /* vad_core.c       kSpectrumWeight                                        */
+  int min_diff[6];               /*                  kMinimumDifference                                     */
+  int max_speech[6];             /*                  kMaximumSpeech                                         */
+  int max_noise[6];              /*                  kMaximumNoise                                          */
+  int min_mean[2];               /*                  kMinimumMean, per Gaussian                             */
+  int noise_weight[12];          /*                  kNoiseDataWeights  [band + 6 * gaussian]               */
+  int speech_weight[12];         /*                  kSpeechDataWeights                                     */
+  int noise_mean[12];            /*                  kNoiseDataMeans                                        */
+  int speech_mean[12];           /*                  kSpeechDataMeans                                       */
+  int noise_std[12];             /*                  kNoiseDataStds                                         */
+  int speech_std[12];            /*                  kSpeechDataStds                                        */
+  int over_hang_1[4];            /* per mode 0 ... 3, the entries for 10 ms frames: kOverHangMax1*[0]       */
+  int over_hang_2[4];            /*                                                  kOverHangMax2*[0]       */
+  int local_thres[4];            /*                                                  kLocalThreshold*[0]     */
+  int global_thres[4];           /*                                                  kGlobalThreshold*[0]    */
+} jamd_fvad_model;
+#define JAMD_FVAD_MODEL_INTS 130 /* entries of jamd_fvad_model, each a 16-bit value                          */
+typedef struct {
+  int sfreq;                     /* 8000 or 16000                                                            */
+  int mode;                      /* -fvad: 0 ... 3                                                           */
+  const jamd_fvad_model *model;  /* copied by _create                                                        */
+} jamd_fvad_desc;
+typedef struct jamd_fvad jamd_fvad;
+/* jamd_fvad_state_get(): the core of one channel as integers, named as in the reference's VadInstT:
+ *   [0..1] downsampling_filter_states[0..1]   [2..13] noise_means   [14..25] speech_means   [26..37] noise_stds
+ *   [38..49] speech_stds   [50] frame_counter   [51] over_hang   [52] num_of_speech   [53..148] index_vector
+ *   [149..244] low_value_vector   [245..250] mean_value   [251..255] upper_state   [256..260] lower_state
+ *   [261..264] hp_filter_state   [265] samples of an incomplete frame that wait on the device */
+#define JAMD_FVAD_STATE_INTS 266
+
+/* host only: the model file, JAMD_FVAD_MODEL_INTS decimal integers in the order of the members above, one per line;
+ * empty lines and lines that begin with '#' are skipped.  JAMD_EINVAL for a file that cannot be read, holds a line that
+ * is no integer or no 16-bit value, or holds fewer or more entries. */
+int  jamd_fvad_model_read(const char *path, jamd_fvad_model *m);
+/* nchan channels, each as fvad_new() + fvad_set_mode() leave it.  JAMD_EINVAL for a rate other than 8000 / 16000 (the
+ * reference ignores fvad_set_sample_rate()'s failure and goes on at 8000; not reproduced), a mode outside 0 ... 3, a
+ * NULL model or a model entry that is no 16-bit value. */
+int  jamd_fvad_create(jamd_engine *e, const jamd_fvad_desc *d, int nchan, jamd_fvad **out);
+void jamd_fvad_destroy(jamd_fvad *f);
+/* The channels with a non-zero byte of mask ([nchan], host; NULL = all) get a fresh core and lose their waiting samples.
+ * Queued on `stream`. */
+int  jamd_fvad_reset(jamd_fvad *f, const unsigned char *mask, void *stream);
+/* host only: frames that a push of `chunk` samples completes on a channel that has taken samples_before since its last
+ * reset: floor((samples_before + chunk) / fs) - floor(samples_before / fs) with fs = sfreq / 100.  Needs sfreq only. */
+int64_t jamd_fvad_frames(const jamd_fvad_desc *d, int64_t samples_before, int64_t chunk);
+/* Channel c appends [in_off[c], in_off[c+1]) of dev_in (host offsets [nchan + 1], as for jamd_adin_push_dev()).  Every
+ * frame that completes is processed; the rest waits on the device.  Per frame one byte, the core's raw value, goes to
+ * dev_out, channel after channel; their host offsets [nchan + 1] into out_off.  The counts are closed-form
+ * (jamd_fvad_frames()), so the call only enqueues.  A channel with an empty chunk is untouched.  One stream per object. */
+int  jamd_fvad_push_dev (jamd_fvad *f, const int16_t *dev_in, const int64_t *in_off, unsigned char *dev_out,
+                         int64_t *out_off, void *stream);
+/* The same from and to host memory, on the engine's stream; `out` has room for the sum of jamd_fvad_frames(). */
+int  jamd_fvad_push_host(jamd_fvad *f, const int16_t *samples, const int64_t *in_off, unsigned char *out, int64_t *out_off);
+/* One channel after everything queued so far (waits for the device): state [JAMD_FVAD_STATE_INTS], in the order above. */
+int  jamd_fvad_state_get(jamd_fvad *f, int chan, int *state);
+
+/* ---- -fvad / -fvad_param inside the silence cutting: the detector gates the zero-cross trigger ----------------
+ * adin_cut() calls fvad_proceed() for every block before it tests the zero-cross count, and the block triggers only if
+ * both hold (adin-cut.c:264-311, :662-668).  fvad_proceed() runs the detector on the 10 ms frames of the stream -- a
+ * frame only once one more sample is there, so max(0, ceil(e / fs) - 1) frames by the end e of a block, on a grid fixed
+ * at the stream's start whatever the blocks are -- and answers whether, of the last `smoothnum` results (zeros before
+ * the first), the mean in float reaches `thres`.  need_init (end of stream, jamd_adin_cut_reset()) clears the results
+ * and the grid but not the detector: fvad_new() is called once and fvad_reset() never, so filter states, adapted models
+ * and hangover run on into the next stream, as the -48 filter state does.  A last whole frame that still waited for
+ * its one more sample at the end of a stream never reaches the detector.
+ * A push runs the detector over exactly the frames the reference has processed by the end of the last block the push
+ * walks, reading samples of earlier pushes out of the channel's history, and commits the detector with the rest of
+ * the state: a push refused for max_parts leaves it where it was. */
+typedef struct {
+  jamd_fvad_desc det;            /* sfreq must be the cutting descriptor's                                  */
+  int   smoothnum;               /* -fvad_param, first argument:  1 ... JAMD_FVAD_SMOOTH_MAX (default.c: 5) */
+  float thres;                   /*              second argument: 0 ... 1 (0.5); 0 never closes the gate    */
+} jamd_adin_cut_fvad;
+#define JAMD_FVAD_SMOOTH_MAX 1000
+/* As jamd_adin_cut_create(), with the gate.  JAMD_EINVAL where that or jamd_fvad_create() refuses, for smoothnum or
+ * thres out of range (the reference clamps with a warning, m_chkparam.c:349-371), for det.sfreq != d->sfreq, and for
+ * chunk_size + sfreq / 100 > 320000 (MAXSPEECHLEN), where fvad_proceed() drops samples. */
+int  jamd_adin_cut_create_fvad(jamd_engine *e, const jamd_adin_cut_desc *d, const jamd_adin_cut_fvad *fv, int nchan,
+                               jamd_adin_cut **out);
+/* The channels with a non-zero byte of mask ([nchan], host; NULL = all) get a fresh detector, as fvad_new() +
+ * fvad_set_mode() leave it; nothing else of them changes.  JAMD_EINVAL for an object without the gate.  Queued on
+ * `stream`. */
+int  jamd_adin_cut_fvad_reset(jamd_adin_cut *k, const unsigned char *mask, void *stream);
+/* The detector of one channel after everything queued so far, as jamd_fvad_state_get() (the last entry is 0: nothing
+ * waits here, the frames are read out of the history). */
+int  jamd_adin_cut_fvad_state_get(jamd_adin_cut *k, int chan, int *state);
 
 #ifdef __cplusplus
 }

@@ -136,8 +136,10 @@ struct AcPlanArgs {
   int cap;
 };
 
-// One lane per channel walks the channel's blocks in order (adin-cut.c:647-984).
-__global__ __launch_bounds__(64) void ac_blocks_kernel(AcDev g, AcPlanArgs a) {
+// One lane per channel walks the channel's blocks in order (adin-cut.c:647-984).  GATE: the block triggers only if
+// fvad_proceed() says so too (:662-668): of the last N frames processed by the block's end, cmin or more were speech.
+template <bool GATE>
+__device__ __forceinline__ void ac_blocks(const AcDev &g, const AcPlanArgs &a, const AcGateDev &v) {
   const int c = blockIdx.x * 64 + threadIdx.x;
   if (c >= g.nchan) return;
   const AcChanTab t = a.tab[c];
@@ -155,6 +157,11 @@ __global__ __launch_bounds__(64) void ac_blocks_kernel(AcDev g, AcPlanArgs a) {
   }
   const long long B = s.pos;
   const unsigned *cnt = a.cnt + t.cnt_off, *hc = a.hc + (size_t)c * g.hist;
+  const long long F0 = GATE ? ac_gate_span(s, t, g.chunk, v.fs).F0 : 0;
+  auto speech_at = [&](long long k) -> unsigned {            // V[k]
+    if (k <= 0) return 0u;
+    return k > F0 ? v.vnew[v.voff[c] + (k - F0 - 1)] : v.vh[(size_t)c * v.vhist + k % v.vhist];
+  };
   auto count_at = [&](long long q) -> unsigned {             // C[q]
     if (q < 0) return 0u;
     return q >= B ? cnt[q - B] : hc[q % g.hist];
@@ -186,7 +193,12 @@ __global__ __launch_bounds__(64) void ac_blocks_kernel(AcDev g, AcPlanArgs a) {
     avail -= w;
     const int zc = (int)(count_at(e - 1) - count_at(e - 1 - g.c_length));
     s.zc = zc;
-    if (zc > g.noise_zc) {
+    bool open = true;
+    if (GATE) {
+      const long long n = fv_gate_frames(e, v.fs);
+      open = (int)(speech_at(n) - speech_at(n - v.N)) >= v.cmin;
+    }
+    if (open && zc > g.noise_zc) {
       if (!s.is_valid) {                                     // trigger: the cycle buffer less this block first
         s.is_valid = 1;
         s.nc = 0;
@@ -234,6 +246,10 @@ __global__ __launch_bounds__(64) void ac_blocks_kernel(AcDev g, AcPlanArgs a) {
   a.next[c] = s;
   a.used[c] = part;
 }
+
+// Without the gate: the kernel, its arguments and its registers are what they were before there was one
+__global__ __launch_bounds__(64) void ac_blocks_kernel(AcDev g, AcPlanArgs a) { ac_blocks<false>(g, a, AcGateDev{}); }
+__global__ __launch_bounds__(64) void ac_blocks_gated_kernel(AcDev g, AcPlanArgs a, AcGateDev v) { ac_blocks<true>(g, a, v); }
 
 // The part count, and per part the offsets of the channels' ranges, part after part.  One workgroup.
 __global__ __launch_bounds__(kThreads) void ac_offsets_kernel(const int *__restrict__ used, const int *__restrict__ pl, int nchan,
@@ -337,7 +353,13 @@ int ac_launch_plan(jamd_adin_cut *k, hipStream_t st, const AcChanTab *d_tab, con
                      k->d_strig, k->d_scum);
   JAMD_HIP(hipGetLastError());
   AcPlanArgs a{d_tab, k->d_state, k->d_cnt, k->d_hc, k->d_strig, k->d_scum, k->d_next, k->d_pa, k->d_pl, k->d_used, t, cap};
-  hipLaunchKernelGGL(ac_blocks_kernel, dim3((nchan + 63) / 64), dim3(64), 0, st, k->g, a);
+  if (k->gate) {
+    const FvGate &q = *k->gate;
+    const AcGateDev v{q.d_vnew, q.d_vh, (const long long *)q.vtab.d.p, q.fs, q.N, q.cmin, q.vhist};
+    hipLaunchKernelGGL(ac_blocks_gated_kernel, dim3((nchan + 63) / 64), dim3(64), 0, st, k->g, a, v);
+  } else {
+    hipLaunchKernelGGL(ac_blocks_kernel, dim3((nchan + 63) / 64), dim3(64), 0, st, k->g, a);
+  }
   JAMD_HIP(hipGetLastError());
   hipLaunchKernelGGL(ac_offsets_kernel, dim3(1), dim3(kThreads), 0, st, k->d_used, k->d_pl, k->nchan, cap, t);
   JAMD_HIP(hipGetLastError());

@@ -4,6 +4,7 @@
 #include "adin_cut_host.h"
 
 constexpr int kAcMaxParts = 65535;                           // (the gather's grid)
+constexpr int kAcMaxSpeechLen = 320000;                      // MAXSPEECHLEN: fvad_proceed()'s buffer
 
 extern "C" {
 
@@ -47,12 +48,29 @@ void jamd_adin_cut_destroy(jamd_adin_cut *k) {
   delete k;                                  // (the engine is not looked at: it may have gone first)
 }
 
-int jamd_adin_cut_create(jamd_engine *e, const jamd_adin_cut_desc *d, int nchan, jamd_adin_cut **out) {
-  if (!e || !d || !out || nchan < 1 || nchan > 65535) return jamd_refuse("jamd_adin_cut_create: NULL argument or nchan not in 1 ... 65535");
+// The object of either entry; fv == NULL: without the gate
+static int ac_create(const char *who, jamd_engine *e, const jamd_adin_cut_desc *d, const jamd_adin_cut_fvad *fv, int nchan,
+                     jamd_adin_cut **out) {
+  if (!e || !d || !out || nchan < 1 || nchan > 65535) return jamd_refuse("%s: NULL argument or nchan not in 1 ... 65535", who);
   *out = nullptr;
   AcParams p;
   std::string err;
-  if (!ac_params(d, p, err)) return jamd_refuse("jamd_adin_cut_create: %s", err.c_str());
+  if (!ac_params(d, p, err)) return jamd_refuse("%s: %s", who, err.c_str());
+  int fs = 0;
+  if (fv) {
+    if (!fv_check_desc(&fv->det, err)) return jamd_refuse("%s: %s", who, err.c_str());
+    if (fv->det.sfreq != d->sfreq)
+      return jamd_refuse("%s: the detector's sfreq (%d) is not the cutting's (%d)", who, fv->det.sfreq, d->sfreq);
+    if (fv->smoothnum < 1 || fv->smoothnum > JAMD_FVAD_SMOOTH_MAX)
+      return jamd_refuse("%s: smoothnum %d is not in 1 ... %d", who, fv->smoothnum, JAMD_FVAD_SMOOTH_MAX);
+    if (!(fv->thres >= 0.0f && fv->thres <= 1.0f)) return jamd_refuse("%s: thres %g is not in 0 ... 1", who, (double)fv->thres);
+    fs = fv_frame_size(d->sfreq);
+    if ((long long)d->chunk_size + fs > kAcMaxSpeechLen)
+      return jamd_refuse("%s: chunk_size %d + a frame of %d samples > %d (MAXSPEECHLEN): fvad_proceed() would drop samples", who,
+                         d->chunk_size, fs, kAcMaxSpeechLen);
+    // a frame that ends in a push can begin chunk_size - 1 + fs samples behind it
+    if (p.hist < d->chunk_size + fs) p.hist = d->chunk_size + fs;
+  }
   std::unique_ptr<jamd_adin_cut> k(new jamd_adin_cut());   // (its members own what they hold)
   k->eng = e; k->nchan = nchan; k->d = *d; k->p = p;
   k->g = AcDev{d->level_thres, d->chunk_size, p.c_length, p.noise_zerocross, p.nc_max, p.sbsize, p.hist, nchan};
@@ -65,7 +83,51 @@ int jamd_adin_cut_create(jamd_engine *e, const jamd_adin_cut_desc *d, int nchan,
       (rc = k->d_strig.alloc(C)) != JAMD_OK || (rc = k->d_scum.alloc(C)) != JAMD_OK || (rc = k->d_used.alloc(C)) != JAMD_OK ||
       (rc = k->d_mask.alloc(C)) != JAMD_OK)
     return rc;
+  if (fv) {
+    k->gate.reset(new FvGate());
+    FvGate &q = *k->gate;
+    q.fs = fs; q.N = fv->smoothnum; q.cmin = fv_gate_cmin(fv->smoothnum, fv->thres); q.vhist = fv->smoothnum + 1;
+    const FvModel m = fv_model(fv->det.model, fv->det.mode);
+    if ((rc = q.d_model.upload(&m, 1)) != JAMD_OK || (rc = q.d_s16.alloc(C * kFvKept)) != JAMD_OK ||
+        (rc = q.d_s16n.alloc(C * kFvKept)) != JAMD_OK || (rc = q.d_s32.alloc(C * 3)) != JAMD_OK ||
+        (rc = q.d_s32n.alloc(C * 3)) != JAMD_OK || (rc = q.d_vh.alloc(C * q.vhist, true)) != JAMD_OK)
+      return rc;
+    if ((rc = fv_launch_reset_at(e->stream, q.d_model, nullptr, q.d_s16, q.d_s32, nullptr, nchan)) != JAMD_OK) return rc;
+    JAMD_HIP(hipStreamSynchronize(e->stream));   // (a push may come on another stream)
+  }
   *out = k.release();
+  return JAMD_OK;
+}
+
+int jamd_adin_cut_create(jamd_engine *e, const jamd_adin_cut_desc *d, int nchan, jamd_adin_cut **out) {
+  return ac_create("jamd_adin_cut_create", e, d, nullptr, nchan, out);
+}
+
+int jamd_adin_cut_create_fvad(jamd_engine *e, const jamd_adin_cut_desc *d, const jamd_adin_cut_fvad *fv, int nchan,
+                              jamd_adin_cut **out) {
+  if (!fv) return jamd_refuse("jamd_adin_cut_create_fvad: the gate's descriptor (fv) is NULL; jamd_adin_cut_create() makes an object without the gate");
+  return ac_create("jamd_adin_cut_create_fvad", e, d, fv, nchan, out);
+}
+
+int jamd_adin_cut_fvad_reset(jamd_adin_cut *k, const unsigned char *mask, void *stream) {
+  if (!k || !k->gate) return jamd_refuse("jamd_adin_cut_fvad_reset: NULL object, or one made without the gate");
+  JAMD_HIP(hipSetDevice(k->eng->device));
+  hipStream_t st = jamd_stream(k->eng, stream);
+  if (mask) JAMD_HIP(hipMemcpyAsync(k->d_mask, mask, (size_t)k->nchan, hipMemcpyHostToDevice, st));
+  return fv_launch_reset_at(st, k->gate->d_model, mask ? k->d_mask.p : nullptr, k->gate->d_s16, k->gate->d_s32, nullptr, k->nchan);
+}
+
+int jamd_adin_cut_fvad_state_get(jamd_adin_cut *k, int chan, int *state) {
+  if (!k || !k->gate || !state || chan < 0 || chan >= k->nchan)
+    return jamd_refuse("jamd_adin_cut_fvad_state_get: NULL argument, an object made without the gate, or channel out of range");
+  JAMD_HIP(hipSetDevice(k->eng->device));
+  JAMD_HIP(hipDeviceSynchronize());
+  const size_t C = k->nchan;
+  short s16[kFvKept];
+  int s32[3];
+  JAMD_HIP(hipMemcpy2D(s16, sizeof(short), k->gate->d_s16 + chan, C * sizeof(short), sizeof(short), kFvKept, hipMemcpyDeviceToHost));
+  JAMD_HIP(hipMemcpy2D(s32, sizeof(int), k->gate->d_s32 + chan, C * sizeof(int), sizeof(int), 3, hipMemcpyDeviceToHost));
+  fv_state_ints(s16, s32, 0, state);
   return JAMD_OK;
 }
 
@@ -90,12 +152,16 @@ int jamd_adin_cut_push_dev(jamd_adin_cut *k, const int16_t *dev_in, const int64_
   JAMD_HIP(hipSetDevice(k->eng->device));
   if ((rc = k->tab.begin(nchan * sizeof(AcChanTab))) != JAMD_OK) return rc;
   AcChanTab *h_ch = (AcChanTab *)k->tab.h.p;
-  long long total = 0, room = 0;
+  FvGate *gate = k->gate.get();
+  if (gate && (rc = gate->vtab.begin(nchan * sizeof(long long))) != JAMD_OK) return rc;
+  long long *h_voff = gate ? (long long *)gate->vtab.h.p : nullptr;
+  long long total = 0, room = 0, vtotal = 0;
   bool any = false;
   for (int c = 0; c < nchan; c++) {
     long long n;
     if ((rc = jamd_span("jamd_adin_cut_push_dev", in_off, c, &n)) != JAMD_OK) return rc;
     h_ch[c] = AcChanTab{in_off[c], total, (int)n, eos && eos[c] ? 1 : 0};
+    if (gate) { h_voff[c] = vtotal; vtotal += ac_gate_frames_cap(n, k->d.chunk_size, gate->fs); }
     total += n;
     if (n > 0 || h_ch[c].eos) { any = true; room += ac_push_cap(&k->d, k->p, n); }
   }
@@ -110,6 +176,12 @@ int jamd_adin_cut_push_dev(jamd_adin_cut *k, const int16_t *dev_in, const int64_
   if ((rc = k->h_tabs.grow(tb)) != JAMD_OK) return rc;
   if ((rc = k->tab.send(nchan * sizeof(AcChanTab), st)) != JAMD_OK) return rc;
   const AcChanTab *d_ch = (const AcChanTab *)k->tab.d.p;
+  const long long *d_voff = gate ? (const long long *)gate->vtab.d.p : nullptr;
+  if (gate) {                                                // the detector first: the blocks read its counts
+    if ((rc = gate->d_vnew.grow((size_t)vtotal * sizeof(unsigned))) != JAMD_OK) return rc;
+    if ((rc = gate->vtab.send(nchan * sizeof(long long), st)) != JAMD_OK) return rc;
+    if ((rc = acg_launch_frames(k, st, d_ch, d_voff, dev_in)) != JAMD_OK) return rc;
+  }
   const AcTabs dt = ac_tabs_at(k->d_tabs.p, nchan, cap), ht = ac_tabs_at(k->h_tabs.p, nchan, cap);
   if ((rc = ac_launch_plan(k, st, d_ch, dev_in, dt, cap)) != JAMD_OK) return rc;
   JAMD_HIP(hipMemcpyAsync(k->h_tabs.p, k->d_tabs, tb, hipMemcpyDeviceToHost, st));
@@ -135,6 +207,7 @@ int jamd_adin_cut_push_dev(jamd_adin_cut *k, const int16_t *dev_in, const int64_
   }
   if (nout > 0 && !dev_out) return jamd_refuse("jamd_adin_cut_push_dev: NULL output");
   if (max_len > 0 && (rc = ac_launch_gather(k, st, d_ch, dev_in, dt, cap, (int)np, max_len, dev_out)) != JAMD_OK) return rc;
+  if (gate && (rc = acg_launch_advance(k, st, d_ch, d_voff)) != JAMD_OK) return rc;
   return ac_launch_advance(k, st, d_ch, dev_in);
 }
 

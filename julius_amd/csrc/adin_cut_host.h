@@ -5,6 +5,7 @@
 #pragma once
 #include "jamd_host.h"
 #include "adin_cut_plan.h"
+#include "fvad_host.h"
 
 // One channel between pushes.  `pos` counts the samples given since the last reset; the last `carried` of them wait for
 // their block to fill.  count_zc_e() runs ahead of the blocks: `trig` (is_trig * 2 + (sign == ZC_NEGATIVE)) and `cum`
@@ -14,6 +15,21 @@ struct AcState { long long pos; unsigned cum; int trig, is_valid, nc, rest_tail,
 struct AcChanTab { long long src_off, cnt_off; int n, eos; };
 // The numbers the kernels take
 struct AcDev { int trigger, chunk, c_length, noise_zc, nc_max, sbsize, hist, nchan; };
+
+// What the blocks kernel reads of the gate (-fvad): V[k] of this push at vnew[voff[c] + k - F0 - 1], older in the ring
+struct AcGateDev { const unsigned *vnew, *vh; const long long *voff; int fs, N, cmin, vhist; };
+// Frames fvad_proceed() has processed by the ends of the last block before a push and of the last block the push walks
+struct AcGateSpan { long long F0, F1; };
+#if defined(__HIPCC__)
+__device__ __forceinline__ AcGateSpan ac_gate_span(const AcState &s, const AcChanTab &t, int chunk, int fs) {
+  const long long e0 = s.pos - s.carried, avail = s.carried + (long long)t.n;
+  const long long e1 = t.eos ? e0 + avail : e0 + avail / chunk * chunk;   // (end of stream: the short last block too)
+  AcGateSpan g{fv_gate_frames(e0, fs), fv_gate_frames(e1, fs)};
+  const long long cap = ac_gate_frames_cap(t.n, chunk, fs);               // (what the host made room for)
+  if (g.F1 - g.F0 > cap) g.F1 = g.F0 + cap;
+  return g;
+}
+#endif
 
 constexpr int kAcTile = 1024;                // samples per step of the scan workgroup
 constexpr int kAcCopyTile = 2048;            // samples per workgroup of the gather
@@ -57,6 +73,7 @@ struct JAMD_LOCAL jamd_adin_cut {
   JamdHostBuf h_tabs;                        // the same, brought down
   JamdPinned tab;                            // AcChanTab [nchan]
   JamdStage<int16_t, int16_t> stage;         // push_host
+  std::unique_ptr<FvGate> gate;              // -fvad: only where jamd_adin_cut_create_fvad() made the object
 };
 
 // ---- adin_cut.hip
@@ -72,3 +89,12 @@ JAMD_LOCAL int ac_launch_gather(jamd_adin_cut *k, hipStream_t st, const AcChanTa
 JAMD_LOCAL int ac_launch_advance(jamd_adin_cut *k, hipStream_t st, const AcChanTab *d_tab, const int16_t *dev_in);
 // The channels d_mask names (NULL: all) back to the start
 JAMD_LOCAL int ac_launch_reset(jamd_adin_cut *k, hipStream_t st, const unsigned char *d_mask);
+
+// ---- adin_cut_fvad.hip (objects with k->gate only)
+// Ahead of ac_launch_plan(): the detector over the frames that fvad_proceed() has seen by the end of the last block
+// this push walks, from k->gate->d_s16 / d_s32 into the next copies, their running speech count -> k->gate->d_vnew at
+// d_voff[c].  Moves no state.
+JAMD_LOCAL int acg_launch_frames(jamd_adin_cut *k, hipStream_t st, const AcChanTab *d_tab, const long long *d_voff,
+                                    const int16_t *dev_in);
+// Ahead of ac_launch_advance(), which ends the push: the next cores become the channels', the newest counts enter the ring
+JAMD_LOCAL int acg_launch_advance(jamd_adin_cut *k, hipStream_t st, const AcChanTab *d_tab, const long long *d_voff);

@@ -58,6 +58,10 @@ static inline bool ac_params(const jamd_adin_cut_desc *d, AcParams &p, std::stri
   return true;
 }
 
+// Frames of fs samples that fvad_proceed() can process in a push of n samples: the blocks the push walks cover less
+// than n + chunk_size samples, and ceil(e / fs) - 1 grows by ceil(that / fs) at the most
+constexpr long long ac_gate_frames_cap(long long n, int chunk_size, int fs) { return (n + chunk_size) / fs + 2; }
+
 // Blocks a push of `chunk` samples can complete: the carry is below chunk_size, and end of stream adds one short block
 static inline long long ac_blocks_cap(const jamd_adin_cut_desc *d, long long chunk) {
   return (chunk + d->chunk_size - 1) / d->chunk_size + 1;

@@ -89,6 +89,43 @@ class AdinCutDesc(C.Structure):
                 ("tail_margin_msec", C.c_int), ("chunk_size", C.c_int)]
 
 
+class FvadModel(C.Structure):
+    """jamd_fvad_model (include/julius_amd.h): libfvad's array constants, handed in by the caller."""
+    _fields_ = [(n, C.c_int * k) for n, k in (
+        ("allpass_q15", 2), ("allpass_q13", 2), ("hp_zero", 3), ("hp_pole", 3), ("offset", 6), ("spectrum_weight", 6),
+        ("min_diff", 6), ("max_speech", 6), ("max_noise", 6), ("min_mean", 2), ("noise_weight", 12), ("speech_weight", 12),
+        ("noise_mean", 12), ("speech_mean", 12), ("noise_std", 12), ("speech_std", 12), ("over_hang_1", 4),
+        ("over_hang_2", 4), ("local_thres", 4), ("global_thres", 4))]
+
+    @classmethod
+    def read(cls, path) -> "FvadModel":
+        """The model file that julius_amd/shim/jamd_fvad_export writes (jamd_fvad_model_read())."""
+        m = cls()
+        _check(load().jamd_fvad_model_read(str(path).encode(), C.byref(m)), "jamd_fvad_model_read")
+        return m
+
+    @classmethod
+    def from_ints(cls, ints) -> "FvadModel":
+        ints = [int(v) for v in ints]
+        assert len(ints) == FVAD_MODEL_INTS
+        return cls.from_buffer_copy((C.c_int * FVAD_MODEL_INTS)(*ints))
+
+    def ints(self):
+        return list((C.c_int * FVAD_MODEL_INTS).from_buffer_copy(self))
+
+
+class FvadDesc(C.Structure):
+    """jamd_fvad_desc (include/julius_amd.h): the rate, -fvad's mode and the model."""
+    _fields_ = [("sfreq", C.c_int), ("mode", C.c_int), ("model", C.POINTER(FvadModel))]
+
+
+class AdinCutFvad(C.Structure):
+    """jamd_adin_cut_fvad (include/julius_amd.h): -fvad's detector and the two arguments of -fvad_param."""
+    _fields_ = [("det", FvadDesc), ("smoothnum", C.c_int), ("thres", C.c_float)]
+
+
+FVAD_MODEL_INTS, FVAD_STATE_INTS = 130, 266
+
 _lib = None
 
 
@@ -245,6 +282,17 @@ def load():
         "jamd_adin_cut_push_dev": (ci, [vp, vp, vp, vp, vp, ci, vp, vp, vp, vp, vp]),
         "jamd_adin_cut_push_host": (ci, [vp, vp, vp, vp, vp, ci, vp, vp, vp, vp]),
         "jamd_adin_cut_state_get": (ci, [vp, ci, vp, vp, vp, vp, vp, vp, vp]),
+        "jamd_adin_cut_create_fvad": (ci, [vp, P(AdinCutDesc), P(AdinCutFvad), ci, P(vp)]),
+        "jamd_adin_cut_fvad_reset": (ci, [vp, vp, vp]),
+        "jamd_adin_cut_fvad_state_get": (ci, [vp, ci, vp]),
+        "jamd_fvad_model_read": (ci, [C.c_char_p, P(FvadModel)]),
+        "jamd_fvad_create": (ci, [vp, P(FvadDesc), ci, P(vp)]),
+        "jamd_fvad_destroy": (None, [vp]),
+        "jamd_fvad_reset": (ci, [vp, vp, vp]),
+        "jamd_fvad_frames": (C.c_int64, [P(FvadDesc), C.c_int64, C.c_int64]),
+        "jamd_fvad_push_dev": (ci, [vp, vp, vp, vp, vp, vp]),
+        "jamd_fvad_push_host": (ci, [vp, vp, vp, vp, vp]),
+        "jamd_fvad_state_get": (ci, [vp, ci, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -1248,12 +1296,42 @@ class AdinCut:
     reference would have passed on by then, cut into parts at segment ends; each part's row of offsets and final flags
     is one LiveFrontend.push_dev()."""
 
-    def __init__(self, eng: Engine, nchan: int, desc: "AdinCutDesc | None" = None, **fields):
+    def __init__(self, eng: Engine, nchan: int, desc: "AdinCutDesc | None" = None, fvad: "AdinCutFvad | None" = None,
+                 **fields):
+        """fvad (AdinCut.fvad_for()): the libfvad detector gates the trigger, as -fvad / -fvad_param do."""
         self.eng, self.nchan = eng, int(nchan)
         self.desc = desc if desc is not None else self.desc_for(**fields)
+        self.fvad = fvad
         h = C.c_void_p()
-        _check(load().jamd_adin_cut_create(eng.h, C.byref(self.desc), self.nchan, C.byref(h)), "jamd_adin_cut_create")
+        if fvad is None:
+            _check(load().jamd_adin_cut_create(eng.h, C.byref(self.desc), self.nchan, C.byref(h)), "jamd_adin_cut_create")
+        else:
+            _check(load().jamd_adin_cut_create_fvad(eng.h, C.byref(self.desc), C.byref(fvad), self.nchan, C.byref(h)),
+                   "jamd_adin_cut_create_fvad")
         self.h = h
+
+    @staticmethod
+    def fvad_for(model, mode: int, smoothnum: int = 5, thres: float = 0.5, sfreq: int = 16000) -> AdinCutFvad:
+        """-fvad `mode` -fvad_param `smoothnum` `thres` with the caller's model (FvadModel)."""
+        f = AdinCutFvad(FvadDesc(int(sfreq), int(mode), C.pointer(model) if model is not None else None), int(smoothnum),
+                        float(thres))
+        f._keep = model                          # (the descriptor borrows the model)
+        return f
+
+    def fvad_reset(self, mask=None, stream: int = 0):
+        """A fresh detector for the channels of mask (None: all); the cutting state stays."""
+        m = None
+        if mask is not None:
+            m = np.ascontiguousarray(np.asarray(mask).astype(bool), dtype=np.uint8)
+            assert len(m) == self.nchan
+        _check(load().jamd_adin_cut_fvad_reset(self.h, m.ctypes.data if m is not None else None, stream or None),
+               "jamd_adin_cut_fvad_reset")
+
+    def fvad_state(self, chan: int) -> np.ndarray:
+        """The detector of one channel as Fvad.state() gives it."""
+        out = np.zeros(FVAD_STATE_INTS, np.int32)
+        _check(load().jamd_adin_cut_fvad_state_get(self.h, int(chan), out.ctypes.data), "jamd_adin_cut_fvad_state_get")
+        return out
 
     @staticmethod
     def desc_for(**fields) -> AdinCutDesc:
@@ -1353,6 +1431,78 @@ class AdinCut:
     def close(self):
         if getattr(self, "h", None):
             load().jamd_adin_cut_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Fvad:
+    """The voice-activity detector behind -fvad (jamd_fvad): libfvad's decision for every 10 ms frame of many channels
+    per call, bit for bit, with every channel's filter states, adapted models, minimum tracker, hangover and the samples
+    of an incomplete frame kept on the device.  A push hands back one byte per completed frame: the core's raw value
+    (0 noise, 1 speech, 2 + the hangover left)."""
+
+    def __init__(self, eng: Engine, nchan: int, model: "FvadModel | None", sfreq: int = 16000, mode: int = 0):
+        self.eng, self.nchan, self.model = eng, int(nchan), model
+        self.desc = self.desc_for(model, sfreq, mode)
+        h = C.c_void_p()
+        _check(load().jamd_fvad_create(eng.h, C.byref(self.desc), self.nchan, C.byref(h)), "jamd_fvad_create")
+        self.h = h
+
+    @staticmethod
+    def desc_for(model, sfreq: int = 16000, mode: int = 0) -> FvadDesc:
+        d = FvadDesc(int(sfreq), int(mode), C.pointer(model) if model is not None else None)
+        d._keep = model                          # (the descriptor borrows the model)
+        return d
+
+    @staticmethod
+    def frames(sfreq: int, samples_before: int, chunk: int) -> int:
+        """Frames a push of `chunk` samples completes behind samples_before (host only)."""
+        d = FvadDesc(int(sfreq), 0, None)
+        n = load().jamd_fvad_frames(C.byref(d), int(samples_before), int(chunk))
+        if n < 0:
+            _check(n, "jamd_fvad_frames")
+        return n
+
+    def reset(self, mask=None, stream: int = 0):
+        m = None
+        if mask is not None:
+            m = np.ascontiguousarray(np.asarray(mask).astype(bool), dtype=np.uint8)
+            assert len(m) == self.nchan
+        _check(load().jamd_fvad_reset(self.h, m.ctypes.data if m is not None else None, stream or None), "jamd_fvad_reset")
+
+    def push_host(self, chunks):
+        """One int16 chunk per channel (empty = idle) -> (raw values back to back uint8, out_off int64 [nchan + 1])."""
+        assert len(chunks) == self.nchan
+        samples, off = Frontend._pack(chunks)
+        out = np.zeros(len(samples) // (self.desc.sfreq // 100) + self.nchan + 1, np.uint8)
+        ooff = np.zeros(self.nchan + 1, np.int64)
+        _check(load().jamd_fvad_push_host(self.h, samples.ctypes.data if len(samples) else None, off.ctypes.data,
+                                          out.ctypes.data, ooff.ctypes.data), "jamd_fvad_push_host")
+        return out[:int(ooff[-1])].copy(), ooff
+
+    def push_dev(self, dev_in: int, in_off, dev_out: int, stream: int = 0):
+        """Device samples in, device bytes out; in_off host int64 [nchan + 1].  Returns out_off int64 [nchan + 1]."""
+        off = np.ascontiguousarray(in_off, dtype=np.int64)
+        assert len(off) == self.nchan + 1
+        ooff = np.zeros(self.nchan + 1, np.int64)
+        _check(load().jamd_fvad_push_dev(self.h, dev_in or None, off.ctypes.data, dev_out or None, ooff.ctypes.data,
+                                         stream or None), "jamd_fvad_push_dev")
+        return ooff
+
+    def state(self, chan: int) -> np.ndarray:
+        """One channel's core as int32 [FVAD_STATE_INTS], in the order stated in julius_amd.h, after everything queued."""
+        out = np.zeros(FVAD_STATE_INTS, np.int32)
+        _check(load().jamd_fvad_state_get(self.h, int(chan), out.ctypes.data), "jamd_fvad_state_get")
+        return out
+
+    def close(self):
+        if getattr(self, "h", None):
+            load().jamd_fvad_destroy(self.h)
             self.h = None
 
     def __del__(self):
