@@ -43,7 +43,7 @@
 // ties == 0 the trellis is the reference's trellis bit for bit.
 //
 // This file holds the kernel and the host functions that know its LDS image (fbeam_layout / fbeam_prepare /
-// fbeam_launch, beam_host.h).  The work area and the C ABI are beam_api.hip's, the lexicon is beam_lexicon.hip's.
+// fbeam_launch, beam_host.h).  The work area and the C ABI are beam_api.hip's, the lexicon is beam_lexicon_api.hip's.
 #include "jamd_device.h"
 #include <type_traits>
 #include <algorithm>

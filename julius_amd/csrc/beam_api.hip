@@ -101,7 +101,7 @@ static int launch_pass1(jamd_beam *b, const float *dev_scores, int nstate, const
   { const int rc = upload_utt_off(b, utt_off, nutt, st); if (rc != JAMD_OK) return rc; }
   { const int rc = mark_started(b, st); if (rc != JAMD_OK) return rc; }
   if (b->order == JAMD_ORDER_STRICT)                        // (keeps no state between launches: whole utterances only)
-    sbeam_launch(b->lex->d, b->w, b->sw, b->lex->multipath, dev_scores, nstate, b->d_utt_off, nutt, st);
+    sbeam_launch(b->lex->d, b->w, b->sm.view, b->lex->multipath, dev_scores, nstate, b->d_utt_off, nutt, st);
   else if (order_is_exact(b))                               // one shape for a whole session: the parked state is the layout's
     xbeam_launch(b->lex->d, xwork_now(b, smode ? b->stream_half : use_half_shape(b, nutt)), dev_scores, nstate, b->d_utt_off,
                  nutt, smode, b->timed, st);
@@ -121,7 +121,7 @@ static int set_order(jamd_beam *b, int mode, const char *who) {
       break;
     case JAMD_ORDER_STRICT: {
       JAMD_HIP(hipSetDevice(b->eng->device));
-      const int rc = sbeam_prepare(&b->sw, b->w, b->lex->multipath, b->max_utts, b->owned);
+      const int rc = sbeam_prepare(&b->sm, b->w, b->lex->multipath, b->max_utts);
       if (rc != JAMD_OK) return rc;
       break;
     }
@@ -135,7 +135,7 @@ static int set_order(jamd_beam *b, int mode, const char *who) {
         return JAMD_ESTATE;
       }
       break;
-    default: jamd_set_error("%s: mode=%d", who, mode); return JAMD_EINVAL;
+    default: return jamd_refuse("%s: mode=%d", who, mode);
   }
   b->order = mode;
   return JAMD_OK;
@@ -145,16 +145,14 @@ extern "C" {
 
 int jamd_beam_create(jamd_engine *e, jamd_lexicon *l, int beam_width, float score_pruning_width,
                      int max_utts, int atoms_per_utt, jamd_beam **out) {
-  if (!e || !l || !out) { jamd_set_error("jamd_beam_create: NULL argument"); return JAMD_EINVAL; }
+  if (!e || !l || !out) return jamd_refuse("jamd_beam_create: NULL argument");
   *out = nullptr;
-  if (beam_width < 1 || beam_width > 65536) {
-    jamd_set_error("jamd_beam_create: beam_width=%d outside [1,65536]", beam_width);
-    return JAMD_EINVAL;
-  }
-  if (max_utts < 1 || atoms_per_utt < 1) { jamd_set_error("jamd_beam_create: bad capacity"); return JAMD_EINVAL; }
+  if (beam_width < 1 || beam_width > 65536) return jamd_refuse("jamd_beam_create: beam_width=%d outside [1,65536]", beam_width);
+  if (max_utts < 1 || atoms_per_utt < 1) return jamd_refuse("jamd_beam_create: bad capacity");
   JAMD_HIP(hipSetDevice(e->device));
-  jamd_beam *b = new jamd_beam();
-  b->eng = e; b->lex = l; b->max_utts = max_utts;
+  std::unique_ptr<jamd_beam> owner(new jamd_beam());
+  jamd_beam *b = owner.get();
+  b->eng = e; b->device = e->device; b->lex = l; b->max_utts = max_utts;
   { const char *tm = getenv("JAMD_BEAM_TIMING"); b->timed = tm != nullptr && atoi(tm) != 0; }
   Work &w = b->w;
   w.beam = beam_width; w.width = score_pruning_width; w.nnode = l->d.nnode; w.nword = l->d.nword;
@@ -162,13 +160,7 @@ int jamd_beam_create(jamd_engine *e, jamd_lexicon *l, int beam_width, float scor
   // every survivor reaches at most maxfan nodes, cross-word candidates only reach roots (multipath: what the roots reach)
   w.tok_cap = beam_width * l->maxfan + l->d.startnum * (l->multipath ? l->maxfan : 1) + l->d.ninit + 1;
   const size_t U = (size_t)max_utts;
-  int rc = JAMD_OK;
-  auto alloc = [&](void **p, size_t bytes, bool zero) -> int {
-    JAMD_HIP(hipMalloc(p, bytes ? bytes : 4));
-    b->owned.push_back(*p);
-    if (zero) JAMD_HIP(hipMemset(*p, 0, bytes));
-    return JAMD_OK;
-  };
+  int rc;
   fbeam_layout(&w);                                  // the canonical-tie kernel's LDS image
   // one slice per utterance: every array at a 256-byte aligned 32-bit offset
   w.nscword = l->nscword > 0 ? l->nscword : 1;
@@ -216,12 +208,13 @@ int jamd_beam_create(jamd_engine *e, jamd_lexicon *l, int beam_width, float scor
       place(&xs.o_key2, (size_t)w.tok_cap * sizeof(unsigned));
     }
   }
-  if (at >= ((size_t)1 << 32)) { jamd_set_error("jamd_beam_create: per-utterance work area exceeds 4 GB"); rc = JAMD_EINVAL; }
+  if (at >= ((size_t)1 << 32)) return jamd_refuse("jamd_beam_create: per-utterance work area exceeds 4 GB");
   w.utt_stride = at;
-  if (rc == JAMD_OK) rc = alloc((void **)&w.slices, U * (size_t)w.utt_stride, true);    // zero: empty Viterbi cells
-  if (rc == JAMD_OK) rc = alloc((void **)&w.res, U * sizeof(jamd_pass1_result), true);
+  if ((rc = b->slices.alloc(U * (size_t)w.utt_stride, true)) != JAMD_OK) return rc;    // zero: empty Viterbi cells
+  if ((rc = b->res.alloc(U, true)) != JAMD_OK) return rc;
+  w.slices = b->slices; w.res = b->res;
   w.resident = nullptr;
-  if (rc == JAMD_OK) {
+  {
     // a counter the first-pass workgroups bump when they start, in signal memory so that another stream's command
     // processor can wait on it (jamd_beam_stream_wait_resident()); JAMD_NO_WAIT_VALUE=1 keeps the host-side wait
     int can = 0;
@@ -230,70 +223,66 @@ int jamd_beam_create(jamd_engine *e, jamd_lexicon *l, int beam_width, float scor
     if (can && !(off && off[0] == '1')) {
       void *p = nullptr;
       if (hipExtMallocWithFlags(&p, 8, hipMallocSignalMemory) == hipSuccess && p) {
-        if (hipMemset(p, 0, 8) == hipSuccess) { b->d_resident = (unsigned *)p; w.resident = b->d_resident; }
-        else (void)hipFree(p);
+        b->d_resident.adopt((unsigned *)p, 8);
+        if (hipMemset(p, 0, 8) == hipSuccess) w.resident = b->d_resident;
+        else b->d_resident.adopt(nullptr, 0);
       }
       (void)hipGetLastError();
     }
   }
-  if (rc == JAMD_OK) {
-    const hipError_t ae = fbeam_prepare();
-    if (ae != hipSuccess) { jamd_set_error("jamd_beam_create: cannot reserve %d bytes of LDS: %s", w.sv_bytes,
-                                           hipGetErrorString(ae)); rc = JAMD_ENODEV; }
+  const hipError_t ae = fbeam_prepare();
+  if (ae != hipSuccess) {
+    jamd_set_error("jamd_beam_create: cannot reserve %d bytes of LDS: %s", w.sv_bytes, hipGetErrorString(ae));
+    return JAMD_ENODEV;
   }
-  if (rc == JAMD_OK) rc = alloc((void **)&b->d_utt_off, (2 * U + 1) * sizeof(int), true);
-  if (rc == JAMD_OK && b->exact_status == 0) {
+  if ((rc = b->d_utt_off.alloc(2 * U + 1, true)) != JAMD_OK) return rc;
+  if (b->exact_status == 0) {
     // once more, over the finished Work and slice offsets: same slices in both shapes, only the LDS image differs
     lay(&b->xw, false);
     if (b->half_status == 0) lay(&b->xw_half, true);
     if (xbeam_prepare() != hipSuccess) b->exact_status = -5;
   }
-  if (rc == JAMD_OK) {
+  {
     // The work area starts in its default order.  For a grammar with a forward DFA that the exact-order kernel cannot
     // serve (beam too wide for the LDS image, a root that reaches a word end, no LDS) that is strict order instead of a
     // refusal: the caller has no beam to call jamd_beam_set_strict_order() on when create fails.
     rc = set_order(b, default_order(b), "jamd_beam_create");
-    if (rc != JAMD_OK) jamd_set_error("jamd_beam_create: a grammar with a forward DFA needs the exact-order or the strict-order kernel; "
-                                      "neither can serve beam %d on this lexicon", w.beam);
+    if (rc != JAMD_OK) {
+      jamd_set_error("jamd_beam_create: a grammar with a forward DFA needs the exact-order or the strict-order kernel; "
+                     "neither can serve beam %d on this lexicon", w.beam);
+      return rc;
+    }
   }
-  if (rc != JAMD_OK) { jamd_beam_destroy(b); return rc; }
-  *out = b;
+  *out = owner.release();
   return JAMD_OK;
 }
 
 void jamd_beam_destroy(jamd_beam *b) {
   if (!b) return;
-  (void)hipSetDevice(b->eng->device);
-  for (void *p : b->owned) (void)hipFree(p);
-  if (b->ev_started) (void)hipEventDestroy(b->ev_started);
-  if (b->d_resident) (void)hipFree(b->d_resident);
-  delete b;
+  (void)hipSetDevice(b->device);
+  delete b;                                  // (the engine is not looked at: it may have gone first)
 }
 
 int jamd_beam_pass1_dev(jamd_beam *b, const float *dev_scores, int nstate, const int *utt_off, int nutt,
                         void *stream) {
-  if (!b || !dev_scores || !utt_off || nstate <= 0) { jamd_set_error("jamd_beam_pass1_dev: bad argument"); return JAMD_EINVAL; }
-  if (nutt < 0 || nutt > b->max_utts) {
-    jamd_set_error("jamd_beam_pass1_dev: nutt=%d exceeds the work area (%d)", nutt, b->max_utts);
-    return JAMD_EINVAL;
-  }
+  if (!b || !dev_scores || !utt_off || nstate <= 0) return jamd_refuse("jamd_beam_pass1_dev: bad argument");
+  if (nutt < 0 || nutt > b->max_utts) return jamd_refuse("jamd_beam_pass1_dev: nutt=%d exceeds the work area (%d)", nutt, b->max_utts);
   for (int u = 0; u < nutt; u++) {
     const int T = utt_off[u + 1] - utt_off[u];
-    if (T < 0 || T > 32767) {   // TRELLIS_ATOM times are short (trellis.h:32-33)
-      jamd_set_error("jamd_beam_pass1_dev: utterance %d has %d frames (limit 32767)", u, T);
-      return JAMD_EINVAL;
-    }
+    if (T < 0 || T > 32767)     // TRELLIS_ATOM times are short (trellis.h:32-33)
+      return jamd_refuse("jamd_beam_pass1_dev: utterance %d has %d frames (limit 32767)", u, T);
   }
   if (nutt == 0) return JAMD_OK;
   return launch_pass1(b, dev_scores, nstate, utt_off, nutt, 0, stream, "jamd_beam_pass1_dev");
 }
 
 int jamd_beam_stream_begin(jamd_beam *b, int nutt) {
-  if (!b || nutt < 1 || nutt > b->max_utts) { jamd_set_error("jamd_beam_stream_begin: bad argument"); return JAMD_EINVAL; }
+  if (!b || nutt < 1 || nutt > b->max_utts) return jamd_refuse("jamd_beam_stream_begin: bad argument");
   JAMD_HIP(hipSetDevice(b->eng->device));
-  void *p = nullptr;
   if (b->w.stream == nullptr) {
-    JAMD_HIP(hipMalloc(&p, sizeof(StreamState) * (size_t)b->max_utts)); b->owned.push_back(p); b->w.stream = (StreamState *)p;
+    const int rc = b->stream.alloc((size_t)b->max_utts);
+    if (rc != JAMD_OK) return rc;
+    b->w.stream = b->stream;
   }
   JAMD_HIP(hipMemsetAsync(b->w.stream, 0, sizeof(StreamState) * (size_t)nutt, b->eng->stream));
   JAMD_HIP(hipStreamSynchronize(b->eng->stream));
@@ -305,17 +294,14 @@ int jamd_beam_stream_begin(jamd_beam *b, int nutt) {
 
 int jamd_beam_stream_push_dev(jamd_beam *b, const float *dev_scores, int nstate, const int *chunk_off, int nutt,
                               int final, void *stream) {
-  if (!b || !chunk_off || nstate <= 0 || (!dev_scores && chunk_off[nutt > 0 ? nutt : 0] > 0)) {
-    jamd_set_error("jamd_beam_stream_push_dev: bad argument"); return JAMD_EINVAL;
-  }
+  if (!b || !chunk_off || nstate <= 0 || (!dev_scores && chunk_off[nutt > 0 ? nutt : 0] > 0)) return jamd_refuse("jamd_beam_stream_push_dev: bad argument");
   if (b->streaming <= 0 || nutt != b->streaming) {
     jamd_set_error("jamd_beam_stream_push_dev: call jamd_beam_stream_begin(b, %d) first", nutt); return JAMD_ESTATE;
   }
   for (int u = 0; u < nutt; u++) {
-    if (chunk_off[u + 1] < chunk_off[u]) { jamd_set_error("jamd_beam_stream_push_dev: chunk_off must be non-decreasing"); return JAMD_EINVAL; }
-    if ((long)b->stream_frames[u] + (chunk_off[u + 1] - chunk_off[u]) > 32767) {   // TRELLIS_ATOM times are short
-      jamd_set_error("jamd_beam_stream_push_dev: utterance %d would exceed 32767 frames", u); return JAMD_EINVAL;
-    }
+    if (chunk_off[u + 1] < chunk_off[u]) return jamd_refuse("jamd_beam_stream_push_dev: chunk_off must be non-decreasing");
+    if ((long)b->stream_frames[u] + (chunk_off[u + 1] - chunk_off[u]) > 32767)     // TRELLIS_ATOM times are short
+      return jamd_refuse("jamd_beam_stream_push_dev: utterance %d would exceed 32767 frames", u);
   }
   if (b->order == JAMD_ORDER_STRICT) {
     if (!final || b->stream_pushes != 0) {
@@ -334,7 +320,7 @@ int jamd_beam_stream_push_dev(jamd_beam *b, const float *dev_scores, int nstate,
 }
 
 int jamd_beam_set_strict_order(jamd_beam *b, int on) {
-  if (!b) { jamd_set_error("jamd_beam_set_strict_order: NULL"); return JAMD_EINVAL; }
+  if (!b) return jamd_refuse("jamd_beam_set_strict_order: NULL");
   // (the parked state of an open session is the layout of the kernel that wrote it)
   if (b->streaming > 0) { jamd_set_error("jamd_beam_set_strict_order: a streaming session is open"); return JAMD_ESTATE; }
   if (!on && default_order(b) == JAMD_ORDER_STRICT) {
@@ -347,17 +333,15 @@ int jamd_beam_set_strict_order(jamd_beam *b, int on) {
 }
 
 int jamd_beam_set_order_mode(jamd_beam *b, int mode) {
-  if (!b) { jamd_set_error("jamd_beam_set_order_mode: NULL"); return JAMD_EINVAL; }
+  if (!b) return jamd_refuse("jamd_beam_set_order_mode: NULL");
   if (b->streaming > 0) { jamd_set_error("jamd_beam_set_order_mode: a streaming session is open"); return JAMD_ESTATE; }
   return set_order(b, mode, "jamd_beam_set_order_mode");
 }
 
 int jamd_beam_set_workgroup_shape(jamd_beam *b, int shape) {
-  if (!b) { jamd_set_error("jamd_beam_set_workgroup_shape: NULL"); return JAMD_EINVAL; }
+  if (!b) return jamd_refuse("jamd_beam_set_workgroup_shape: NULL");
   if (b->streaming > 0) { jamd_set_error("jamd_beam_set_workgroup_shape: a streaming session is open"); return JAMD_ESTATE; }
-  if (shape != JAMD_SHAPE_AUTO && shape != JAMD_SHAPE_FULL && shape != JAMD_SHAPE_HALF) {
-    jamd_set_error("jamd_beam_set_workgroup_shape: shape=%d", shape); return JAMD_EINVAL;
-  }
+  if (shape != JAMD_SHAPE_AUTO && shape != JAMD_SHAPE_FULL && shape != JAMD_SHAPE_HALF) return jamd_refuse("jamd_beam_set_workgroup_shape: shape=%d", shape);
   if (shape == JAMD_SHAPE_HALF && b->half_status != 0) {
     jamd_set_error("jamd_beam_set_workgroup_shape: beam %d does not fit the half shape (%s)", b->w.beam,
                    b->exact_status != 0 ? "the exact-order kernel cannot serve this work area" : "half a CU's LDS holds no typical frame");
@@ -368,7 +352,7 @@ int jamd_beam_set_workgroup_shape(jamd_beam *b, int shape) {
 }
 
 int jamd_beam_wait_started(jamd_beam *b) {
-  if (!b) { jamd_set_error("jamd_beam_wait_started: NULL"); return JAMD_EINVAL; }
+  if (!b) return jamd_refuse("jamd_beam_wait_started: NULL");
   if (!b->ev_started) return JAMD_OK;                  // nothing launched yet
   JAMD_HIP(hipSetDevice(b->eng->device));
   JAMD_HIP(hipEventSynchronize(b->ev_started));
@@ -376,7 +360,7 @@ int jamd_beam_wait_started(jamd_beam *b) {
 }
 
 int jamd_beam_stream_wait_resident(jamd_beam *b, void *stream) {
-  if (!b) { jamd_set_error("jamd_beam_stream_wait_resident: NULL"); return JAMD_EINVAL; }
+  if (!b) return jamd_refuse("jamd_beam_stream_wait_resident: NULL");
   if (!b->ev_started) return JAMD_OK;                  // nothing launched yet
   JAMD_HIP(hipSetDevice(b->eng->device));
   if (b->d_resident) {
@@ -392,7 +376,7 @@ int jamd_beam_stream_wait_resident(jamd_beam *b, void *stream) {
 }
 
 int jamd_beam_debug_preset_resident(jamd_beam *b, unsigned count) {
-  if (!b) { jamd_set_error("jamd_beam_debug_preset_resident: NULL"); return JAMD_EINVAL; }
+  if (!b) return jamd_refuse("jamd_beam_debug_preset_resident: NULL");
   JAMD_HIP(hipSetDevice(b->eng->device));
   JAMD_HIP(hipDeviceSynchronize());
   if (b->d_resident) JAMD_HIP(hipMemcpy(b->d_resident, &count, sizeof(unsigned), hipMemcpyHostToDevice));
@@ -401,7 +385,7 @@ int jamd_beam_debug_preset_resident(jamd_beam *b, unsigned count) {
 }
 
 int jamd_beam_debug_resident(const jamd_beam *b, unsigned *launched, unsigned *target) {
-  if (!b) { jamd_set_error("jamd_beam_debug_resident: NULL"); return JAMD_EINVAL; }
+  if (!b) return jamd_refuse("jamd_beam_debug_resident: NULL");
   if (launched) *launched = b->launched_wg;
   if (target) *target = b->resident_target;
   return JAMD_OK;
@@ -423,20 +407,22 @@ int jamd_beam_order_mode(const jamd_beam *b) {
 }
 
 static int prune_order_impl(jamd_beam *b, const float *scores, int n, int *order, int *nkeep, int *arr) {
-  if (!b || !scores || !order || !nkeep || n < 1) { jamd_set_error("jamd_beam_prune_order: bad argument"); return JAMD_EINVAL; }
+  if (!b || !scores || !order || !nkeep || n < 1) return jamd_refuse("jamd_beam_prune_order: bad argument");
   if (b->exact_status != 0) { jamd_set_error("jamd_beam_prune_order: the exact-order kernel cannot serve this work area"); return JAMD_ESTATE; }
-  if (n > (1 << 20)) { jamd_set_error("jamd_beam_prune_order: n=%d too large", n); return JAMD_EINVAL; }
+  if (n > (1 << 20)) return jamd_refuse("jamd_beam_prune_order: n=%d too large", n);
   JAMD_HIP(hipSetDevice(b->eng->device));
+  int rc;
   if ((size_t)n > b->pcap) {
-    void *p = nullptr;
+    // The old buffers go when the new ones come: nothing is in flight, every call has synchronised its stream before it
+    // returned.  pcap is 0 until both are there.
     const size_t cap = ((size_t)n + 1024 + 3) & ~(size_t)3;     // multiple of 4: the heap and the top-list scratch stay aligned
-    JAMD_HIP(hipMalloc(&p, cap * 4)); b->owned.push_back(p); b->d_pkeys = (unsigned *)p;
+    b->pcap = 0;
+    if ((rc = b->d_pkeys.grow(cap * 4)) != JAMD_OK) return rc;
     // out[cap] + nout (+ pad) | heap u64[cap + 2] | top-list scratch u32x4[beam + 256] (wide layout) | sweep replay scratch
-    JAMD_HIP(hipMalloc(&p, 4 * (cap + 16) + 8 * (cap + 2) + 16 * ((size_t)b->w.beam + 256) + xbeam_sweep_bytes(b->w.beam))); b->owned.push_back(p); b->d_pout = (int *)p;
+    if ((rc = b->d_pout.grow(4 * (cap + 16) + 8 * (cap + 2) + 16 * ((size_t)b->w.beam + 256) + xbeam_sweep_bytes(b->w.beam))) != JAMD_OK) return rc;
     b->pcap = cap;
-    b->d_parr = nullptr;
   }
-  if (arr && !b->d_parr) { void *p = nullptr; JAMD_HIP(hipMalloc(&p, 4 * b->pcap)); b->owned.push_back(p); b->d_parr = (int *)p; }
+  if (arr && (rc = b->d_parr.grow(4 * b->pcap)) != JAMD_OK) return rc;
   std::vector<unsigned> keys((size_t)n);
   for (int i = 0; i < n; i++) {
     float f = scores[i] + 0.0f; unsigned u; memcpy(&u, &f, 4);
@@ -448,7 +434,7 @@ static int prune_order_impl(jamd_beam *b, const float *scores, int n, int *order
   unsigned long long *d_heap = reinterpret_cast<unsigned long long *>(b->d_pout + b->pcap + 16);
   u32x4 *d_collect = reinterpret_cast<u32x4 *>(d_heap + b->pcap + 2);
   unsigned char *d_sweep = reinterpret_cast<unsigned char *>(d_collect + (size_t)b->w.beam + 256);
-  xbeam_prune_order_launch(xwork_now(b, !arr && use_half_shape(b, 1)), b->d_pkeys, n, b->w.beam, b->d_pout, d_nout, d_heap, d_collect, d_sweep, arr ? b->d_parr : nullptr, st);
+  xbeam_prune_order_launch(xwork_now(b, !arr && use_half_shape(b, 1)), b->d_pkeys, n, b->w.beam, b->d_pout, d_nout, d_heap, d_collect, d_sweep, arr ? b->d_parr.p : nullptr, st);
   hipError_t le = hipGetLastError();
   if (le != hipSuccess) { jamd_set_error("jamd_beam_prune_order: launch failed: %s", hipGetErrorString(le)); return JAMD_ELAUNCH; }
   JAMD_HIP(hipMemcpyAsync(nkeep, d_nout, 4, hipMemcpyDeviceToHost, st));
@@ -464,12 +450,12 @@ int jamd_beam_prune_order(jamd_beam *b, const float *scores, int n, int *order, 
 }
 
 int jamd_beam_prune_arrange(jamd_beam *b, const float *scores, int n, int *order, int *nkeep, int *tindex) {
-  if (!tindex) { jamd_set_error("jamd_beam_prune_arrange: bad argument"); return JAMD_EINVAL; }
+  if (!tindex) return jamd_refuse("jamd_beam_prune_arrange: bad argument");
   return prune_order_impl(b, scores, n, order, nkeep, tindex);
 }
 
 int jamd_beam_prune_stats(jamd_beam *b, int utt, int stats[16], int reset) {
-  if (!b || !stats || utt < 0 || utt >= b->max_utts) { jamd_set_error("jamd_beam_prune_stats: bad argument"); return JAMD_EINVAL; }
+  if (!b || !stats || utt < 0 || utt >= b->max_utts) return jamd_refuse("jamd_beam_prune_stats: bad argument");
   if (b->exact_status != 0) { jamd_set_error("jamd_beam_prune_stats: the exact-order kernel does not serve this work area"); return JAMD_ESTATE; }
   JAMD_HIP(hipSetDevice(b->eng->device));
   unsigned char *p = b->w.slices + (size_t)utt * b->w.utt_stride + b->xw.o_pstat;
@@ -479,7 +465,7 @@ int jamd_beam_prune_stats(jamd_beam *b, int utt, int stats[16], int reset) {
 }
 
 int jamd_beam_prune_info(jamd_beam *b, int *sweep_rounds, int *sweep_us, int *sweep_events) {
-  if (!b || !sweep_rounds || !b->d_pout) { jamd_set_error("jamd_beam_prune_info: bad argument (or no jamd_beam_prune_order() call yet)"); return JAMD_EINVAL; }
+  if (!b || !sweep_rounds || !b->d_pout) return jamd_refuse("jamd_beam_prune_info: bad argument (or no jamd_beam_prune_order() call yet)");
   JAMD_HIP(hipSetDevice(b->eng->device));
   int v[15];
   JAMD_HIP(hipMemcpy(v, b->d_pout + b->pcap + 1, sizeof(v), hipMemcpyDeviceToHost));
@@ -493,7 +479,7 @@ int jamd_beam_prune_info(jamd_beam *b, int *sweep_rounds, int *sweep_us, int *sw
 }
 
 int jamd_beam_results(jamd_beam *b, jamd_pass1_result *out, int nutt) {
-  if (!b || !out || nutt < 0 || nutt > b->max_utts) { jamd_set_error("jamd_beam_results: bad argument"); return JAMD_EINVAL; }
+  if (!b || !out || nutt < 0 || nutt > b->max_utts) return jamd_refuse("jamd_beam_results: bad argument");
   JAMD_HIP(hipSetDevice(b->eng->device));
   JAMD_HIP(hipDeviceSynchronize());
   if (nutt) JAMD_HIP(hipMemcpy(out, b->w.res, sizeof(jamd_pass1_result) * nutt, hipMemcpyDeviceToHost));
@@ -501,7 +487,7 @@ int jamd_beam_results(jamd_beam *b, jamd_pass1_result *out, int nutt) {
 }
 
 int jamd_beam_trellis(jamd_beam *b, int utt, jamd_trellis_atom *atoms, int cap, int *natom) {
-  if (!b || !natom || utt < 0 || utt >= b->max_utts) { jamd_set_error("jamd_beam_trellis: bad argument"); return JAMD_EINVAL; }
+  if (!b || !natom || utt < 0 || utt >= b->max_utts) return jamd_refuse("jamd_beam_trellis: bad argument");
   JAMD_HIP(hipSetDevice(b->eng->device));
   JAMD_HIP(hipDeviceSynchronize());
   jamd_pass1_result r;

@@ -3,6 +3,7 @@
 // installed.
 #pragma once
 #include "beam_common.h"
+#include "jamd_host.h"
 
 namespace jamdb {
 
@@ -50,14 +51,14 @@ struct XWork {
 // half = the half shape: 512 threads and half a CU's LDS, so that two utterances share a CU and one's barriers and
 // wave-serial sections overlap the other's work (-2 when a typical frame would not fit that image).
 // mp = multipath lexicon (nroot = the roots a word end is followed by: isolated roots under an N-gram, all under a grammar).
-int xbeam_layout(XWork *xw, const Work &w, int maxfan, int nroot, int ninit, int nshared, bool half, bool mp = false);
+JAMD_LOCAL int xbeam_layout(XWork *xw, const Work &w, int maxfan, int nroot, int ninit, int nshared, bool half, bool mp = false);
 // places the per-launch part of the image (cells, pruning overlay, score row of nstate floats or none)
-void xbeam_place(XWork *xw, int nstate);
-hipError_t xbeam_prepare();
-void xbeam_launch(const LexDev &lx, const XWork &xw, const float *scores, int nstate, const int *d_utt_off, int nutt,
+JAMD_LOCAL void xbeam_place(XWork *xw, int nstate);
+JAMD_LOCAL hipError_t xbeam_prepare();
+JAMD_LOCAL void xbeam_launch(const LexDev &lx, const XWork &xw, const float *scores, int nstate, const int *d_utt_off, int nutt,
                   int smode, bool timed, hipStream_t st);
-void xbeam_prune_order_launch(const XWork &xw, const unsigned *d_keys, int n, int k, int *d_out, int *d_nout,
+JAMD_LOCAL void xbeam_prune_order_launch(const XWork &xw, const unsigned *d_keys, int n, int k, int *d_out, int *d_nout,
                               unsigned long long *d_hglob, u32x4 *d_collect, unsigned char *d_sweep, int *d_arr, hipStream_t st);
-size_t xbeam_sweep_bytes(int beam);   // global scratch of the sweep replay per utterance
+JAMD_LOCAL size_t xbeam_sweep_bytes(int beam);   // global scratch of the sweep replay per utterance
 
 }  // namespace jamdb

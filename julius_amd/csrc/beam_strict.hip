@@ -364,17 +364,17 @@ beam_strict_kernel(LexDev lx, Work wk, StrictWork sw, const float *__restrict__ 
 
 namespace jamdb {
 
-int sbeam_prepare(StrictWork *sw, const Work &w, bool multipath, int max_utts, std::vector<void *> &owned) {
-  if (sw->token != nullptr) return JAMD_OK;
+int sbeam_prepare(StrictMem *sm, const Work &w, bool multipath, int max_utts) {
+  if (sm->view.token != nullptr) return JAMD_OK;
   const size_t U = (size_t)max_utts;
   // a node holds at most one token per frame; multipath frames also create tokens behind every root
-  sw->cap = multipath ? w.nnode + 2 : w.tok_cap + 2;
-  void *p = nullptr;
+  const int cap = multipath ? w.nnode + 2 : w.tok_cap + 2;
+  int rc;
   for (int i = 0; i < 2; i++) {
-    JAMD_HIP(hipMalloc(&p, U * sw->cap * sizeof(STok))); owned.push_back(p); sw->tl[i] = (STok *)p;
-    JAMD_HIP(hipMalloc(&p, U * sw->cap * sizeof(int))); owned.push_back(p); sw->ti[i] = (int *)p;
+    if ((rc = sm->tl[i].alloc(U * cap)) != JAMD_OK || (rc = sm->ti[i].alloc(U * cap)) != JAMD_OK) return rc;
   }
-  JAMD_HIP(hipMalloc(&p, U * w.nnode * sizeof(int))); owned.push_back(p); sw->token = (int *)p;
+  if ((rc = sm->token.alloc(U * w.nnode)) != JAMD_OK) return rc;
+  sm->view = StrictWork{{sm->tl[0], sm->tl[1]}, {sm->ti[0], sm->ti[1]}, sm->token, cap};   // (token last: set = all of it is there)
   return JAMD_OK;
 }
 

@@ -42,6 +42,11 @@ struct JAMD_LOCAL JamdDev {
     cap = bytes;
     return JAMD_OK;
   }
+  // Takes over `bytes` at `q` that came from another allocator whose memory hipFree() releases (signal memory).
+  void adopt(T *q, size_t bytes) {
+    if (p) (void)hipFree(p);
+    p = q; cap = bytes;
+  }
   // n elements, zeroed if asked.  No table is NULL: an empty one still gets 16 bytes.
   int alloc(size_t n, bool zero = false) {
     int rc;

@@ -11,7 +11,9 @@ instruction text (addresses and encodings stripped); it lists what differs and e
 The exact-order first-pass kernels (--filter beam_exact, --filter prune_order) are all compiled by csrc/beam_exact.hip, from
 beam_exact_dev.h, beam_prune.h, beam_sweep.h and beam_exact_mp.h.  A call of a function that is not inlined is encoded
 relative to the call site, so moving a kernel to another unit -- or changing the order of the kernels in one -- changes its
-text here even when nothing else does.
+text here even when nothing else does.  The other first-pass kernels: csrc/beam.hip compiles beam_pass1_kernel, csrc/beam_strict.hip
+beam_strict_kernel, and csrc/beam_lexicon.hip iwtab_build_kernel (--filter iwtab_build) and nothing else: the lexicon's
+host layer is csrc/beam_lexicon_api.hip over beam_lexicon_image.h, which contain no kernel.
 
 The scoring kernels (--filter gmm_, --filter tmix_, --filter rejgmm, --filter gms_): csrc/gmm_outprob.hip compiles K1
 (gmm_tile_kernel), its generic-D and narrow forms and gmm_dens_kernel, csrc/gmm_pruned.hip K1s (gmm_safe_kernel), K2 and
