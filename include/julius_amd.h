@@ -147,7 +147,8 @@ int  jamd_gmm_veclen(const jamd_gmm *g);
  * frames is [T][veclen] row-major, out is [T][nstate] row-major (the
  * outprob_cache layout, outprob.c:127-129).
  * The model's device scratch (the per-Gaussian scores of a call of at most 256 frames, the codebook cache of a
- * tied-mixture model, the staged utterance boundaries) is reused by every call: calls on one jamd_gmm must not be in
+ * tied-mixture model, the staged utterance boundaries, the eight ticket heads from which the waves of a long call's
+ * scoring kernel draw their tiles, zeroed on `stream` ahead of it) is reused by every call: calls on one jamd_gmm must not be in
  * flight on two streams at once -- queue them on one stream (they are then ordered), or use one object per stream.
  * The first call of at most 256 frames allocates its scratch (256 x the model's mixture entries, floats); a growing
  * codebook cache allocates as well: such a call is not free of device allocation. */

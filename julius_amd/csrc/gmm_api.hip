@@ -122,6 +122,7 @@ int jamd_gmm_create(jamd_engine *e, const jamd_gmm_desc *d, int gprune, int gpru
         for (int k = 0; k < 8; k++) { q[16 * c + k] = r[8 * c - 1 + k]; q[16 * c + 8 + k] = r[D + 8 * c - 1 + k]; }
     }
     if ((rc = g->d_rec_ring.upload(ring.data(), ring.size())) != JAMD_OK) return rc;
+    if ((rc = jamd_gmm_pull_setup(g.get())) != JAMD_OK) return rc;
   }
   if ((rc = g->d_st_off.upload(d->st_off, g->S + 1)) != JAMD_OK) return rc;
   if ((rc = g->d_st_off_plain.upload(st_off_plain.data(), g->S + 1)) != JAMD_OK) return rc;

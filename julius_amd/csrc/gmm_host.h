@@ -39,6 +39,11 @@ struct JAMD_LOCAL jamd_gmm {
   JamdDev<float> d_tm_score; JamdDev<int> d_tm_id, d_tm_num;
   JamdDev<float> d_narrow;        // [kNarrowT][E_plain] weighted Gaussian scores of a narrow call (K1n, gmm_outprob.hip)
   JamdDev<int> d_tm_flag;         // [T][nbook] gprune safe: (frame, codebook)s whose list depends on the visiting order
+  // K1's pull form (D = 39; gmm_deal.h, gmm_outprob.hip), set up once by jamd_gmm_pull_setup()
+  JamdDev<int> d_pull_heads;      // eight ticket heads, one per 128-byte line, zeroed on the call's stream before a pull launch
+  int pull_cap = 0;               // blocks of the pull kernel the device holds at once, rounded down to a multiple of 8
+  int pull_min = 0;               // the pull form serves a call of more blocks than this (negative: never)
+  int pull_grid = 0;              // blocks of a pull launch when > 0 (development), else pull_cap
   char last_kernel[64] = {0};
 };
 
@@ -46,6 +51,9 @@ struct JAMD_LOCAL jamd_gmm {
 // ---- gmm_outprob.hip
 // Plain states, every Gaussian (gprune none): K1, or K1n for a call of a handful of frames, or the generic-D kernel.
 JAMD_LOCAL int jamd_gmm_launch_plain(jamd_gmm *g, const float *frames, int T, float *out, hipStream_t st);
+// Once per model, from jamd_gmm_create(): what K1's pull form needs (the ticket heads, the device's capacity for the
+// model's instantiation, the two development switches), so that the stream-ordered call allocates and asks nothing.
+JAMD_LOCAL int jamd_gmm_pull_setup(jamd_gmm *g);
 // Per-Gaussian scores out[T][E] of the E records at `rec` (the plain entries or the codebook Gaussians).
 JAMD_LOCAL int jamd_gmm_launch_dens(jamd_gmm *g, const float *rec, int E, const float *frames, int T, float *out,
                                         hipStream_t st);

@@ -32,6 +32,7 @@
 // forms of K1 (jamd_gmm_launch_plain).  The host layer that calls them is gmm_api.hip (see gmm_host.h).
 #include "gmm_dev.h"
 #include "gmm_host.h"
+#include "gmm_deal.h"
 
 namespace {
 using namespace jamd;
@@ -186,7 +187,7 @@ gmm_tile_kernel(const float *__restrict__ rec, const int *__restrict__ st_off,
 // the wait moves registers the load has not written yet: a result that is wrong only sometimes.  Hence THE RULE OF
 // THIS KERNEL: every wait stands in the same basic block as the loads it retires, before any branch or join -- the
 // second wait is the last statement of the loop body, the prologue's wait is inside its `if` -- and no statement
-// between a load and its wait names the home.  profiles/gmm_ring_loop_isa.txt holds the loop of both instantiations as
+// between a load and its wait names the home.  profiles/gmm_ring_loop_isa.txt holds the loop of all four instantiations as
 // compiled; check it again after any change here (no instruction between an s_load_dwordx16 and the next
 // s_waitcnt lgkmcnt(0) may name the load's destination registers).
 //
@@ -221,91 +222,129 @@ __device__ __forceinline__ void ring_chunk(f2 &acc, const f2 *v, const f16v &h) 
   }
 }
 
-template <int NS, bool HAS_NULL>
+// PULL: the same kernel for a launch of as many blocks as the device holds at once (launch_tile).  What the other form
+// takes from its block index -- one (state range, frames) tile per wave -- a wave here draws from a ticket counter, tile
+// after tile until none is left (gmm_deal.h): everything from `s_begin` on is the body of that loop, the ring's `held`
+// carries over tickets as it does over states, and nothing in a tile depends on which wave computes it or when.  The
+// four waves of a block share nothing but the LDS array (tile[wave] is private) and never wait for each other.
+template <int NS, bool HAS_NULL, bool PULL>
 __global__ void __launch_bounds__(64 * kWaves)
 gmm_tile_ring_kernel(const float *__restrict__ ring, const int *__restrict__ st_off,
                      const float *__restrict__ frames, const float *__restrict__ tbl,
                      float *__restrict__ out, int T, int S, int nsb, int nfb, int nstb,
-                     float addmin_f) {
+                     float addmin_f, int *__restrict__ heads) {
   constexpr int D = 39, FPL = 2;
   constexpr int FPW = 64 * FPL;
   __shared__ float tile[kWaves][FPW][NS + 1];
 
-  int fb, sb;
-  if (!decode_block(nfb, nstb, fb, sb)) return;
   const int lane = threadIdx.x & 63;
   const int wave = threadIdx.x >> 6;
-  const int t0 = (fb * kWaves + wave) * FPW;
-  if (t0 >= T) return;  // whole wave out of range (no block-level barriers below)
-
   f2 v[D];
-  load_frames<D>(v, nullptr, frames, t0, T, D, lane);
+  int sb, t0;
+  if constexpr (!PULL) {
+    int fb;
+    if (!decode_block(nfb, nstb, fb, sb)) return;
+    t0 = (fb * kWaves + wave) * FPW;
+    if (t0 >= T) return;  // whole wave out of range (no block-level barriers below)
+    load_frames<D>(v, nullptr, frames, t0, T, D, lane);
+  }
 
   // (the addlog table as a raw buffer: see gmm_tile_kernel)
   const __amdgpu_buffer_rsrc_t tbl_rsrc = __builtin_amdgcn_make_buffer_rsrc((void *)tbl, 0, 4 * (JAMD_TBLSIZE + 1), 0x00020000);
   const float naddmin = -addmin_f;
-  const int s_begin = sb * nsb;
-  const int s_end = min(S, s_begin + nsb);
+  // PULL: the wave's share of the deal (gmm_deal.h; nfb holds the launch's groups of FPW frames) and the shares it has
+  // found exhausted
+  int share = blockIdx.x & (kGdShares - 1), spent = 0;
   f16v h0, h1, h2;             // the ring: chunks 0 / 1 / 2 of record `held` at the top of a Gaussian
   int held = -1;
-  for (int sg = s_begin; sg < s_end; sg += NS) {
-    const int ns = min(NS, s_end - sg);
-    for (int si = 0; si < ns; si++) {
-      const int s = sg + si;
-      const int e0 = st_off[s], e1 = st_off[s + 1];
-      // the record behind this state's first entry: the next state's last one (its own last one when that state is
-      // empty: a valid record, and `held` sends the state after it through the prologue), or this state's last again
-      const int e_over = (s + 1 < s_end ? st_off[s + 2] : e1) - 1;
-      f2 y2 = {JAMD_LOG_ZERO, JAMD_LOG_ZERO}, tv2 = {0.0f, 0.0f};   // running log-sum and pending table term
-      if (e1 > e0 && held != e1 - 1) {
-        const float *r = ring + (size_t)(e1 - 1) * kRingRec;
-        ring_load<0>(h0, r);
-        ring_load<64>(h1, r);
-        ring_load<128>(h2, r);
-        ring_wait(h0, h1, h2);     // inside the `if`: see the rule above
+  for (;;) {
+    if constexpr (PULL) {
+      // Take a ticket: lane 0 draws the next number of the wave's share (one returning add on the share's head, relaxed,
+      // device scope: the number is all that is communicated); a number past the share's end sends the wave on to the
+      // next share for good (a share never grows again), and after eight such finds there is no tile left anywhere.
+      // Which wave computes a tile changes nothing in the tile: the result does not depend on the draw.
+      const GmmDeal deal = gd_make(nstb, nfb);
+      int group = 0;
+      bool got = false;
+      while (spent < kGdShares) {
+        int n = 0;
+        if (lane == 0) n = __hip_atomic_fetch_add(heads + share * kGdHeadStride, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        n = __builtin_amdgcn_readfirstlane(n);
+        got = gd_ticket(deal, share, n, sb, group);
+        if (got) break;
+        share = (share + 1) & (kGdShares - 1);
+        spent++;
       }
-      for (int e = e1 - 1; e >= e0; e--) {
-        const float *r = ring + (size_t)e * kRingRec;
-        const float *rn = ring + (size_t)(e > e0 ? e - 1 : e_over) * kRingRec;
-        const float gc = h0[0], lw = h0[1];
-        const bool nulld = HAS_NULL && (gc != gc);  // NULL density marker (gprune_none.c:67)
-        f2 acc = {gc, gc};
-        ring_chunk<7, 2, 9>(acc, v, h0);
-        ring_load<192>(h0, r);
-        ring_chunk<8, 0, 8>(acc, v + 7, h1);
-        ring_load<256>(h1, r);
-        ring_chunk<8, 0, 8>(acc, v + 15, h2);
-        ring_wait(h0, h1, h2);
-        ring_chunk<8, 0, 8>(acc, v + 23, h0);
-        ring_load<0>(h0, rn);
-        ring_load<128>(h2, rn);
-        ring_chunk<8, 0, 8>(acc, v + 31, h1);
-        ring_load<64>(h1, rn);
-        {
-          // the log-sum step of gmm_tile_kernel (see the notes there), for the lane's one frame pair
-          f2 s2 = acc * f2{-0.5f, -0.5f};
-          if (nulld) s2 = f2{JAMD_LOG_ZERO, JAMD_LOG_ZERO};
-          s2 = s2 + f2{lw, lw};
-          __builtin_amdgcn_sched_barrier(0);     // keep the wait for the gathered term behind the D-loop
-          const f2 yy = y2 + tv2;
-          const f2 hi = {__builtin_fmaxf(s2.x, yy.x), __builtin_fmaxf(s2.y, yy.y)};
-          const f2 df = s2 - yy;
-          const float a0 = __builtin_fabsf(df.x), a1 = __builtin_fabsf(df.y);
-          unsigned o0 = ((unsigned)((double)a0 * JAMD_TMAG + 0.5)) << 2, o1 = ((unsigned)((double)a1 * JAMD_TMAG + 0.5)) << 2;
-          o0 = (a0 <= naddmin) ? o0 : 4u * (unsigned)JAMD_TBLSIZE;
-          o1 = (a1 <= naddmin) ? o1 : 4u * (unsigned)JAMD_TBLSIZE;
-          tv2 = f2{__builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(tbl_rsrc, (int)o0, 0, 0)),
-                   __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(tbl_rsrc, (int)o1, 0, 0))};
-          y2 = hi;
-        }
-        ring_wait(h0, h1, h2);     // the last statement of the body: see the rule above
-      }
-      if (e1 > e0) held = e_over;
-      const f2 fin = y2 + tv2;
-      tile[wave][lane][si] = finish_state(fin.x);
-      tile[wave][64 + lane][si] = finish_state(fin.y);
+      if (!got) return;
+      t0 = group * FPW;
+      // The frames are loaded for every ticket, as a block of the other form loads them for its one tile.  Keeping them
+      // when the new ticket names the group already held would need `v` carried round this loop past a conditional
+      // load: compiled, that is two copies of the 78 registers (183 VGPRs, or scratch under a 128-register bound), and
+      // a share runs over a range's groups first (at least three in a pull launch), so a wave's next ticket names another group.
+      load_frames<D>(v, nullptr, frames, t0, T, D, lane);
     }
-    store_tile<NS, FPW>(tile[wave], out, t0, T, S, sg, ns, lane);
+    const int s_begin = sb * nsb;
+    const int s_end = min(S, s_begin + nsb);
+    for (int sg = s_begin; sg < s_end; sg += NS) {
+      const int ns = min(NS, s_end - sg);
+      for (int si = 0; si < ns; si++) {
+        const int s = sg + si;
+        const int e0 = st_off[s], e1 = st_off[s + 1];
+        // the record behind this state's first entry: the next state's last one (its own last one when that state is
+        // empty: a valid record, and `held` sends the state after it through the prologue), or this state's last again
+        const int e_over = (s + 1 < s_end ? st_off[s + 2] : e1) - 1;
+        f2 y2 = {JAMD_LOG_ZERO, JAMD_LOG_ZERO}, tv2 = {0.0f, 0.0f};   // running log-sum and pending table term
+        if (e1 > e0 && held != e1 - 1) {
+          const float *r = ring + (size_t)(e1 - 1) * kRingRec;
+          ring_load<0>(h0, r);
+          ring_load<64>(h1, r);
+          ring_load<128>(h2, r);
+          ring_wait(h0, h1, h2);     // inside the `if`: see the rule above
+        }
+        for (int e = e1 - 1; e >= e0; e--) {
+          const float *r = ring + (size_t)e * kRingRec;
+          const float *rn = ring + (size_t)(e > e0 ? e - 1 : e_over) * kRingRec;
+          const float gc = h0[0], lw = h0[1];
+          const bool nulld = HAS_NULL && (gc != gc);  // NULL density marker (gprune_none.c:67)
+          f2 acc = {gc, gc};
+          ring_chunk<7, 2, 9>(acc, v, h0);
+          ring_load<192>(h0, r);
+          ring_chunk<8, 0, 8>(acc, v + 7, h1);
+          ring_load<256>(h1, r);
+          ring_chunk<8, 0, 8>(acc, v + 15, h2);
+          ring_wait(h0, h1, h2);
+          ring_chunk<8, 0, 8>(acc, v + 23, h0);
+          ring_load<0>(h0, rn);
+          ring_load<128>(h2, rn);
+          ring_chunk<8, 0, 8>(acc, v + 31, h1);
+          ring_load<64>(h1, rn);
+          {
+            // the log-sum step of gmm_tile_kernel (see the notes there), for the lane's one frame pair
+            f2 s2 = acc * f2{-0.5f, -0.5f};
+            if (nulld) s2 = f2{JAMD_LOG_ZERO, JAMD_LOG_ZERO};
+            s2 = s2 + f2{lw, lw};
+            __builtin_amdgcn_sched_barrier(0);     // keep the wait for the gathered term behind the D-loop
+            const f2 yy = y2 + tv2;
+            const f2 hi = {__builtin_fmaxf(s2.x, yy.x), __builtin_fmaxf(s2.y, yy.y)};
+            const f2 df = s2 - yy;
+            const float a0 = __builtin_fabsf(df.x), a1 = __builtin_fabsf(df.y);
+            unsigned o0 = ((unsigned)((double)a0 * JAMD_TMAG + 0.5)) << 2, o1 = ((unsigned)((double)a1 * JAMD_TMAG + 0.5)) << 2;
+            o0 = (a0 <= naddmin) ? o0 : 4u * (unsigned)JAMD_TBLSIZE;
+            o1 = (a1 <= naddmin) ? o1 : 4u * (unsigned)JAMD_TBLSIZE;
+            tv2 = f2{__builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(tbl_rsrc, (int)o0, 0, 0)),
+                     __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(tbl_rsrc, (int)o1, 0, 0))};
+            y2 = hi;
+          }
+          ring_wait(h0, h1, h2);     // the last statement of the body: see the rule above
+        }
+        if (e1 > e0) held = e_over;
+        const f2 fin = y2 + tv2;
+        tile[wave][lane][si] = finish_state(fin.x);
+        tile[wave][64 + lane][si] = finish_state(fin.y);
+      }
+      store_tile<NS, FPW>(tile[wave], out, t0, T, S, sg, ns, lane);
+    }
+    if constexpr (!PULL) break;
   }
 }
 
@@ -353,6 +392,10 @@ gmm_tile_generic_kernel(const float *__restrict__ rec, const int *__restrict__ s
   }
 }
 
+constexpr int kNarrowT = 256;      // calls of at most this many frames go to K1n (below; its scratch is kNarrowT x E floats)
+constexpr int kPullNS = 16;        // the tile width K1 is launched with (jamd_gmm_launch_plain)
+constexpr int kPullRounds = 8;     // rounds of blocks from which a call takes the pull form (jamd_gmm_pull_setup)
+
 template <int D, int FPL, int NS>
 int launch_tile(jamd_gmm *g, const float *frames, int T, float *out, hipStream_t st) {
   constexpr int FPB = kWaves * 64 * FPL;
@@ -371,14 +414,35 @@ int launch_tile(jamd_gmm *g, const float *frames, int T, float *out, hipStream_t
   const int grid = xcd_grid(nstb, nfb);
   if constexpr (D == 39 && FPL == 2) {
     // the record-ring form of the kernel (above); the suffix keeps measurements taken on the other form apart
+    static_assert(NS == kPullNS, "jamd_gmm_pull_setup() asks the occupancy of this instantiation");
+    // A call of many rounds of blocks (23 504 blocks against 1 024 resident at the bench shape) is served by the
+    // PULL form: as many blocks as are resident together, whose waves draw (state range, 128-frame group) tiles from
+    // the per-XCD ticket heads until none is left -- a wave slot is refilled when ITS tile ends, not when the slowest
+    // of a block's four does, no block is dispatched after the first round, and the launch drains by single tiles.
+    // Shorter calls keep the block form below as it is (the threshold: jamd_gmm_pull_setup).
+    if (g->pull_min >= 0 && T > kNarrowT && (long long)nstb * nfb > g->pull_min) {
+      const int nfw = (T + 64 * FPL - 1) / (64 * FPL);
+      const int pgrid = gd_pull_grid(g->pull_cap, g->pull_grid);
+      JAMD_HIP(hipMemsetAsync(g->d_pull_heads, 0, sizeof(int) * kGdShares * kGdHeadStride, st));
+      if (g->has_null)
+        hipLaunchKernelGGL((gmm_tile_ring_kernel<NS, true, true>), dim3(pgrid), dim3(64 * kWaves), 0, st,
+                           g->d_rec_ring, g->d_st_off_plain, frames, g->eng->d_addlog, out, T, g->S, nsb, nfw,
+                           nstb, g->eng->addmin_f, g->d_pull_heads);
+      else
+        hipLaunchKernelGGL((gmm_tile_ring_kernel<NS, false, true>), dim3(pgrid), dim3(64 * kWaves), 0, st,
+                           g->d_rec_ring, g->d_st_off_plain, frames, g->eng->d_addlog, out, T, g->S, nsb, nfw,
+                           nstb, g->eng->addmin_f, g->d_pull_heads);
+      snprintf(g->last_kernel, sizeof(g->last_kernel), "gmm_tile<D=%d,FPL=%d,NS=%d,ring,pull> grid=%d nsb=%d", D, FPL, NS, pgrid, nsb);
+      return JAMD_OK;
+    }
     if (g->has_null)
-      hipLaunchKernelGGL((gmm_tile_ring_kernel<NS, true>), dim3(grid), dim3(64 * kWaves), 0, st,
+      hipLaunchKernelGGL((gmm_tile_ring_kernel<NS, true, false>), dim3(grid), dim3(64 * kWaves), 0, st,
                          g->d_rec_ring, g->d_st_off_plain, frames, g->eng->d_addlog, out, T, g->S, nsb, nfb,
-                         nstb, g->eng->addmin_f);
+                         nstb, g->eng->addmin_f, (int *)nullptr);
     else
-      hipLaunchKernelGGL((gmm_tile_ring_kernel<NS, false>), dim3(grid), dim3(64 * kWaves), 0, st,
+      hipLaunchKernelGGL((gmm_tile_ring_kernel<NS, false, false>), dim3(grid), dim3(64 * kWaves), 0, st,
                          g->d_rec_ring, g->d_st_off_plain, frames, g->eng->d_addlog, out, T, g->S, nsb, nfb,
-                         nstb, g->eng->addmin_f);
+                         nstb, g->eng->addmin_f, (int *)nullptr);
     snprintf(g->last_kernel, sizeof(g->last_kernel), "gmm_tile<D=%d,FPL=%d,NS=%d,ring> grid=%d nsb=%d", D, FPL, NS, grid, nsb);
   } else {
     if (g->has_null)
@@ -422,7 +486,6 @@ int launch_tile_generic(jamd_gmm *g, const float *frames, int T, float *out, hip
 // Gaussian scores go to a [T][E] scratch (coalesced), and a second kernel -- one lane per (frame, state) -- runs the
 // table log-sum from the last mixture to the first (addlog_array(), addlog.c:103) and calc_mix()'s tail.  Same four
 // separately rounded fp32 operations per dimension, same scan order: bit-identical to K1 (tests/test_gmm_gpu.py).
-constexpr int kNarrowT = 256;      // calls of at most this many frames (the scratch is kNarrowT x E floats)
 constexpr int kNarrowFB = 8;       // frames per block of the first kernel
 template <int D, bool HAS_NULL>
 __global__ void __launch_bounds__(64)
@@ -556,6 +619,27 @@ gmm_dens_kernel(const float *__restrict__ rec, const float *__restrict__ frames,
 
 
 // entry points used by gmm_api.hip
+int jamd_gmm_pull_setup(jamd_gmm *g) {
+  if (g->D != 39) return JAMD_OK;      // the record-ring kernel alone has a pull form
+  int rc, per_cu = 0;
+  if ((rc = g->d_pull_heads.alloc(kGdShares * kGdHeadStride, true)) != JAMD_OK) return rc;
+  if (g->has_null) JAMD_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, gmm_tile_ring_kernel<kPullNS, true, true>, 64 * kWaves, 0));
+  else JAMD_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, gmm_tile_ring_kernel<kPullNS, false, true>, 64 * kWaves, 0));
+  g->pull_cap = (per_cu * g->eng->num_cu) & ~7;       // (4 x 256 = 1 024 on MI355X)
+  if (g->pull_cap < 8) g->pull_cap = 8;
+  // A call takes the pull form from eight rounds of blocks on.  Below one round there is no turnover to save; up to a
+  // few rounds the pull form LOSES: the tiles of the last, partial round go to the waves that ask first, so some CUs
+  // take four tiles per SIMD and others none, where the dispatcher spreads a partial round of blocks over all CUs
+  // (single calls, 3 000 states, pull / block: 2 048 frames, 0.73 rounds, 1.23; 8 000 frames, 2.9 rounds, 1.07;
+  // 16 000, 5.9 rounds, 1.005; 32 000, 11.6 rounds, 0.973; 64 000, 23 rounds, 0.968 -- profiles/ab_gmm_pull.txt).
+  g->pull_min = kPullRounds * g->pull_cap;
+  // Development switches, read once per model: JAMD_GMM_PULL_MIN = the block count above which the pull form is used
+  // (0: every call of more than kNarrowT frames; negative: never), JAMD_GMM_PULL_GRID = blocks of a pull launch.
+  if (const char *s = getenv("JAMD_GMM_PULL_MIN")) g->pull_min = atoi(s);
+  if (const char *s = getenv("JAMD_GMM_PULL_GRID")) g->pull_grid = atoi(s);
+  return JAMD_OK;
+}
+
 int jamd_gmm_launch_plain(jamd_gmm *g, const float *frames, int T, float *out, hipStream_t st) {
   // a handful of frames: one lane per mixture entry instead of one lane per frame (K1n above) -- where there is an
   // entry (a model whose plain states are all empty has none: K1 writes their LOG_ZERO) and a templated vector length

@@ -8,8 +8,12 @@ kernel's comment states, checked on that text.
 For each instantiation: the per-Gaussian loop (the innermost block holding five s_load_dwordx16) and every other block
 with such a load (the prologue) are walked from each load to the next `s_waitcnt lgkmcnt(0)`: that wait has to come
 before the block ends, and no instruction in between may name one of the load's sixteen destination registers.  Counts
-of the loop (packed operations, waits, s_nop, distance from the youngest load to each wait) are printed with it; the
-exit status is 1 when the rule is broken."""
+of the loop (packed operations, waits, s_nop, distance from the youngest load to each wait) are printed with it.
+
+Four instantiations are expected: <NS, HAS_NULL, PULL> for HAS_NULL and PULL false / true.  The per-Gaussian loop of a
+PULL instantiation has to show the same packed-operation count, the same waits and the same distances as the plain one
+with the same HAS_NULL, and no v_readlane / v_writelane: what the ticket loop needs in SGPRs may be saved outside the
+Gaussian loop, never inside it.  The exit status is 1 when the rule or one of these is broken."""
 import argparse
 import re
 import sys
@@ -90,7 +94,7 @@ def main():
     ap.add_argument("asm")
     ap.add_argument("-o", "--out")
     a = ap.parse_args()
-    report, failed, seen = [], False, 0
+    report, failed, seen, loops = [], False, 0, {}
     for name, body in functions(open(a.asm).readlines()):
         seen += 1
         report.append(f"==== {name}")
@@ -112,8 +116,20 @@ def main():
             report += ["     " + b for b in bad]
             if nload == 5:
                 report += ["\t" + c for c in ins]
-    if seen != 2:
-        report.append(f"expected two instantiations of gmm_tile_ring_kernel, found {seen}"); failed = True
+                if any(o.startswith(("v_readlane", "v_writelane")) for o in ops):
+                    report.append("     SGPR SAVE OR RESTORE INSIDE THE PER-GAUSSIAN LOOP"); failed = True
+                m = re.search(r"ILi\d+ELb([01])ELb([01])E", name)     # <NS, HAS_NULL, PULL>
+                if m:
+                    loops[(m.group(1), m.group(2))] = (sum(o.startswith("v_pk_") for o in ops),
+                                                       sum(c.startswith("s_waitcnt") and "lgkmcnt" in c for c in ins), dist)
+    if seen != 4:
+        report.append(f"expected four instantiations of gmm_tile_ring_kernel, found {seen}"); failed = True
+    for null in "01":
+        plain, pull = loops.get((null, "0")), loops.get((null, "1"))
+        same = plain is not None and plain == pull
+        report.append(f"==== HAS_NULL={null}: per-Gaussian loop of the PULL instantiation (packed operations, waits, distances) "
+                      f"{pull} vs plain {plain}: " + ("same" if same else "DIFFERENT"))
+        failed |= not same
     text = "\n".join(report) + "\n"
     if a.out:
         open(a.out, "w").write(text)
