@@ -44,7 +44,9 @@ struct JAMD_LOCAL jamd_gmm {
   int pull_cap = 0;               // blocks of the pull kernel the device holds at once, rounded down to a multiple of 8
   int pull_min = 0;               // the pull form serves a call of more blocks than this (negative: never)
   int pull_grid = 0;              // blocks of a pull launch when > 0 (development), else pull_cap
-  char last_kernel[64] = {0};
+  int pull_tail = -1;             // tiles at the end of every share dealt in pieces (gmm_deal.h); negative: the default
+  int pull_sub = 0;               // states of such a piece; 0: kGdSub (gd_tail_make)
+  char last_kernel[96] = {0};
 };
 
 // (The two older launchers keep the linkage they had.)

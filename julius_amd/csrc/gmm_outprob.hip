@@ -224,15 +224,17 @@ __device__ __forceinline__ void ring_chunk(f2 &acc, const f2 *v, const f16v &h) 
 
 // PULL: the same kernel for a launch of as many blocks as the device holds at once (launch_tile).  What the other form
 // takes from its block index -- one (state range, frames) tile per wave -- a wave here draws from a ticket counter, tile
-// after tile until none is left (gmm_deal.h): everything from `s_begin` on is the body of that loop, the ring's `held`
-// carries over tickets as it does over states, and nothing in a tile depends on which wave computes it or when.  The
-// four waves of a block share nothing but the LDS array (tile[wave] is private) and never wait for each other.
+// after tile until none is left (gmm_deal.h): everything from the state loop on is the body of that loop, the ring's
+// `held` carries over tickets as it does over states, and nothing in a tile depends on which wave computes it or when.
+// The four waves of a block share nothing but the LDS array (tile[wave] is private) and never wait for each other.
+// A ticket names its states (s_begin, s_end): the last tail_q tiles of every share are drawn in pieces of tail_sub
+// states, so that the launch ends on quarter tiles and not on whole ones (the block form ignores both arguments).
 template <int NS, bool HAS_NULL, bool PULL>
 __global__ void __launch_bounds__(64 * kWaves)
 gmm_tile_ring_kernel(const float *__restrict__ ring, const int *__restrict__ st_off,
                      const float *__restrict__ frames, const float *__restrict__ tbl,
                      float *__restrict__ out, int T, int S, int nsb, int nfb, int nstb,
-                     float addmin_f, int *__restrict__ heads) {
+                     float addmin_f, int *__restrict__ heads, int tail_q, int tail_sub) {
   constexpr int D = 39, FPL = 2;
   constexpr int FPW = 64 * FPL;
   __shared__ float tile[kWaves][FPW][NS + 1];
@@ -240,7 +242,7 @@ gmm_tile_ring_kernel(const float *__restrict__ ring, const int *__restrict__ st_
   const int lane = threadIdx.x & 63;
   const int wave = threadIdx.x >> 6;
   f2 v[D];
-  int sb, t0;
+  int sb, t0, s_begin, s_end;
   if constexpr (!PULL) {
     int fb;
     if (!decode_block(nfb, nstb, fb, sb)) return;
@@ -263,15 +265,24 @@ gmm_tile_ring_kernel(const float *__restrict__ ring, const int *__restrict__ st_
       // device scope: the number is all that is communicated); a number past the share's end sends the wave on to the
       // next share for good (a share never grows again), and after eight such finds there is no tile left anywhere.
       // Which wave computes a tile changes nothing in the tile: the result does not depend on the draw.
+      // The last tail_q tiles of a share come in pieces of tail_sub states (gd_tail_ticket): the ticket names its states,
+      // and a piece that begins behind the model's last state (a short last range) is an empty ticket -- the wave draws
+      // again, before any frame is loaded.
       const GmmDeal deal = gd_make(nstb, nfb);
+      const GmmTail tail = gd_tail_make(tail_q, nsb, tail_sub);
       int group = 0;
       bool got = false;
       while (spent < kGdShares) {
-        int n = 0;
+        int n = 0, s0 = 0, cnt = 0;
         if (lane == 0) n = __hip_atomic_fetch_add(heads + share * kGdHeadStride, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         n = __builtin_amdgcn_readfirstlane(n);
-        got = gd_ticket(deal, share, n, sb, group);
-        if (got) break;
+        if (gd_tail_ticket(deal, tail, share, n, sb, group, s0, cnt)) {
+          s_begin = sb * nsb + s0;
+          s_end = min(S, s_begin + cnt);
+          got = s_begin < S;
+          if (got) break;
+          continue;
+        }
         share = (share + 1) & (kGdShares - 1);
         spent++;
       }
@@ -282,9 +293,10 @@ gmm_tile_ring_kernel(const float *__restrict__ ring, const int *__restrict__ st_
       // load: compiled, that is two copies of the 78 registers (183 VGPRs, or scratch under a 128-register bound), and
       // a share runs over a range's groups first (at least three in a pull launch), so a wave's next ticket names another group.
       load_frames<D>(v, nullptr, frames, t0, T, D, lane);
+    } else {
+      s_begin = sb * nsb;
+      s_end = min(S, s_begin + nsb);
     }
-    const int s_begin = sb * nsb;
-    const int s_end = min(S, s_begin + nsb);
     for (int sg = s_begin; sg < s_end; sg += NS) {
       const int ns = min(NS, s_end - sg);
       for (int si = 0; si < ns; si++) {
@@ -394,7 +406,7 @@ gmm_tile_generic_kernel(const float *__restrict__ rec, const int *__restrict__ s
 
 constexpr int kNarrowT = 256;      // calls of at most this many frames go to K1n (below; its scratch is kNarrowT x E floats)
 constexpr int kPullNS = 16;        // the tile width K1 is launched with (jamd_gmm_launch_plain)
-constexpr int kPullRounds = 8;     // rounds of blocks from which a call takes the pull form (jamd_gmm_pull_setup)
+constexpr int kPullRounds = 5;     // rounds of blocks from which a call takes the pull form (jamd_gmm_pull_setup)
 
 template <int D, int FPL, int NS>
 int launch_tile(jamd_gmm *g, const float *frames, int T, float *out, hipStream_t st) {
@@ -418,31 +430,35 @@ int launch_tile(jamd_gmm *g, const float *frames, int T, float *out, hipStream_t
     // A call of many rounds of blocks (23 504 blocks against 1 024 resident at the bench shape) is served by the
     // PULL form: as many blocks as are resident together, whose waves draw (state range, 128-frame group) tiles from
     // the per-XCD ticket heads until none is left -- a wave slot is refilled when ITS tile ends, not when the slowest
-    // of a block's four does, no block is dispatched after the first round, and the launch drains by single tiles.
-    // Shorter calls keep the block form below as it is (the threshold: jamd_gmm_pull_setup).
+    // of a block's four does, no block is dispatched after the first round, and the launch drains by quarter tiles
+    // (when the heads run dry every slot is somewhere inside its last ticket; a whole tile lasts 400 us at the bench
+    // shape).  Shorter calls keep the block form below as it is (the threshold: jamd_gmm_pull_setup).
     if (g->pull_min >= 0 && T > kNarrowT && (long long)nstb * nfb > g->pull_min) {
       const int nfw = (T + 64 * FPL - 1) / (64 * FPL);
       const int pgrid = gd_pull_grid(g->pull_cap, g->pull_grid);
+      // the end of every share in pieces (gmm_deal.h): by default twice as many tiles as wave slots start on the share,
+      // in quarters (profiles/ab_gmm_tail.txt)
+      const GmmTail tail = gd_tail_make(g->pull_tail >= 0 ? g->pull_tail : gd_tail_default(pgrid), nsb, g->pull_sub);
       JAMD_HIP(hipMemsetAsync(g->d_pull_heads, 0, sizeof(int) * kGdShares * kGdHeadStride, st));
       if (g->has_null)
         hipLaunchKernelGGL((gmm_tile_ring_kernel<NS, true, true>), dim3(pgrid), dim3(64 * kWaves), 0, st,
                            g->d_rec_ring, g->d_st_off_plain, frames, g->eng->d_addlog, out, T, g->S, nsb, nfw,
-                           nstb, g->eng->addmin_f, g->d_pull_heads);
+                           nstb, g->eng->addmin_f, g->d_pull_heads, tail.q, tail.sub);
       else
         hipLaunchKernelGGL((gmm_tile_ring_kernel<NS, false, true>), dim3(pgrid), dim3(64 * kWaves), 0, st,
                            g->d_rec_ring, g->d_st_off_plain, frames, g->eng->d_addlog, out, T, g->S, nsb, nfw,
-                           nstb, g->eng->addmin_f, g->d_pull_heads);
-      snprintf(g->last_kernel, sizeof(g->last_kernel), "gmm_tile<D=%d,FPL=%d,NS=%d,ring,pull> grid=%d nsb=%d", D, FPL, NS, pgrid, nsb);
+                           nstb, g->eng->addmin_f, g->d_pull_heads, tail.q, tail.sub);
+      snprintf(g->last_kernel, sizeof(g->last_kernel), "gmm_tile<D=%d,FPL=%d,NS=%d,ring,pull> grid=%d nsb=%d tail=%dx%d", D, FPL, NS, pgrid, nsb, tail.q, tail.sub);
       return JAMD_OK;
     }
     if (g->has_null)
       hipLaunchKernelGGL((gmm_tile_ring_kernel<NS, true, false>), dim3(grid), dim3(64 * kWaves), 0, st,
                          g->d_rec_ring, g->d_st_off_plain, frames, g->eng->d_addlog, out, T, g->S, nsb, nfb,
-                         nstb, g->eng->addmin_f, (int *)nullptr);
+                         nstb, g->eng->addmin_f, (int *)nullptr, 0, 0);
     else
       hipLaunchKernelGGL((gmm_tile_ring_kernel<NS, false, false>), dim3(grid), dim3(64 * kWaves), 0, st,
                          g->d_rec_ring, g->d_st_off_plain, frames, g->eng->d_addlog, out, T, g->S, nsb, nfb,
-                         nstb, g->eng->addmin_f, (int *)nullptr);
+                         nstb, g->eng->addmin_f, (int *)nullptr, 0, 0);
     snprintf(g->last_kernel, sizeof(g->last_kernel), "gmm_tile<D=%d,FPL=%d,NS=%d,ring> grid=%d nsb=%d", D, FPL, NS, grid, nsb);
   } else {
     if (g->has_null)
@@ -627,16 +643,21 @@ int jamd_gmm_pull_setup(jamd_gmm *g) {
   else JAMD_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, gmm_tile_ring_kernel<kPullNS, false, true>, 64 * kWaves, 0));
   g->pull_cap = (per_cu * g->eng->num_cu) & ~7;       // (4 x 256 = 1 024 on MI355X)
   if (g->pull_cap < 8) g->pull_cap = 8;
-  // A call takes the pull form from eight rounds of blocks on.  Below one round there is no turnover to save; up to a
-  // few rounds the pull form LOSES: the tiles of the last, partial round go to the waves that ask first, so some CUs
-  // take four tiles per SIMD and others none, where the dispatcher spreads a partial round of blocks over all CUs
-  // (single calls, 3 000 states, pull / block: 2 048 frames, 0.73 rounds, 1.23; 8 000 frames, 2.9 rounds, 1.07;
-  // 16 000, 5.9 rounds, 1.005; 32 000, 11.6 rounds, 0.973; 64 000, 23 rounds, 0.968 -- profiles/ab_gmm_pull.txt).
+  // A call takes the pull form from five rounds of blocks on.  With whole tiles to the end the form lost up to a few
+  // rounds (the tiles of the last, partial round go to the waves that ask first: 2 048 frames 1.23, 8 000 frames 1.07,
+  // profiles/ab_gmm_pull.txt); with the tail in quarters the last tickets are short and it mostly does not (single calls,
+  // 3 000 states, pull / block: 2 048 frames, 0.73 rounds, 0.986; 4 000, 1.5 rounds, 0.995; 8 000, 2.9 rounds, 1.005;
+  // 16 000, 5.9 rounds, 0.976; 32 000, 11.6 rounds, 0.956 -- profiles/ab_gmm_tail.txt).  8 000 frames is still slower
+  // beyond the block form's spread, so the threshold lies between 2.9 and 5.9 rounds, on the side measured to win.
   g->pull_min = kPullRounds * g->pull_cap;
   // Development switches, read once per model: JAMD_GMM_PULL_MIN = the block count above which the pull form is used
   // (0: every call of more than kNarrowT frames; negative: never), JAMD_GMM_PULL_GRID = blocks of a pull launch.
   if (const char *s = getenv("JAMD_GMM_PULL_MIN")) g->pull_min = atoi(s);
   if (const char *s = getenv("JAMD_GMM_PULL_GRID")) g->pull_grid = atoi(s);
+  // JAMD_GMM_PULL_TAIL = the tiles at the end of every share that are dealt in pieces (0: none, the deal of whole tiles;
+  // unset: the default of launch_tile), JAMD_GMM_PULL_SUB = states of a piece (2, 4 or 8; measurement only).
+  if (const char *s = getenv("JAMD_GMM_PULL_TAIL")) g->pull_tail = atoi(s) < 0 ? 0 : atoi(s);
+  if (const char *s = getenv("JAMD_GMM_PULL_SUB")) { const int v = atoi(s); if (v == 2 || v == 4 || v == 8) g->pull_sub = v; }
   return JAMD_OK;
 }
 

@@ -36,11 +36,11 @@ def counters(name, sub):
 
 g = counters("gmm", "gmm_tile")
 fetch, write = g["FETCH_SIZE"] * 1024.0, g["WRITE_SIZE"] * 1024.0
-gm = {"kernel": "gmm_tile<D=39,FPL=2,NS=16,ring,pull> grid=1024 nsb=16", "rocprof_kernel_name": g["rocprof_kernel_name"],
+gm = {"kernel": "gmm_tile<D=39,FPL=2,NS=16,ring,pull> grid=1024 nsb=16 tail=1024x4", "rocprof_kernel_name": g["rocprof_kernel_name"],
       "frames_per_launch": 64000,
       "source": f"profiles/{rnd}_gmm_traffic_pmc_summary.json (rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE, separate passes, bench.py --workload gmm "
                 "--steps 3 --warmup 1 --no-cpu-baseline --no-small-T: 64 utterances x 1000 frames per launch), the record-ring kernel in its "
-                "pull form (1 024 resident blocks whose waves draw the 94 000 tiles from the per-XCD ticket heads); 'kernel' is the string gmm.last_kernel() reports, which bench.py requires to match",
+                "pull form (1 024 resident blocks whose waves draw the 94 000 tiles from the per-XCD ticket heads, the last 1 024 tiles of every share in quarters); 'kernel' is the string gmm.last_kernel() reports, which bench.py requires to match",
       "FETCH_SIZE_KB_avg_per_dispatch": g["FETCH_SIZE"], "WRITE_SIZE_KB_avg_per_dispatch": g["WRITE_SIZE"],
       "correction": "MI355X_MICROARCH.md 'HBM': on gfx950 FETCH_SIZE tallies 128-B requests at 64 B -> doubled (wide coalesced reads); WRITE_SIZE as reported (the [T][S] output is 768.0 MB)",
       "hbm_bytes_per_launch": int(2 * fetch + write), "kernel_ms_under_pmc": g.get("avg_ms")}
