@@ -475,6 +475,9 @@ int  jamd_bingram_check(const char *lex_path, const char *bingram_path, int *sam
 /* Host only: the 1-gram factoring values jamd_lexicon_load_ngram() would use -- fscore[0..*nfscore) (at most `cap` are
  * written; index 0 is unused, as in WCHMM_INFO.fscore) -- with the same acceptance rules and errors. */
 int  jamd_bingram_fscore(const char *lex_path, const char *bingram_path, float *fscore, int cap, int *nfscore);
+/* Diagnostic: 1 = the cross-word LM table exists, 0 = the first-pass kernels compute its entries as they need them (a
+ * grammar or word list, a table past 2 GB, an allocation that failed, JAMD_NO_IWTAB), -1 = NULL. */
+int  jamd_lexicon_lm_table(const jamd_lexicon *l);
 void jamd_lexicon_destroy(jamd_lexicon *l);
 
 /* First-pass status of one utterance */

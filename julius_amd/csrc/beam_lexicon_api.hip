@@ -32,7 +32,9 @@ int jamd_lexicon_create(jamd_engine *e, const jamd_lexicon_desc *h, jamd_lexicon
   { const int rc = l->arena.upload(im.arena.data(), im.arena.size()); if (rc != JAMD_OK) return rc; }
   d.base = l->arena;
   const size_t cells = (size_t)h->ng_nword * h->isolatenum;
-  if (d.lm_type == JAMD_LM_NGRAM && cells > 0 && cells * sizeof(float) <= kIwTabMaxBytes) {
+  const char *no_tab = getenv("JAMD_NO_IWTAB");    // (development: the table-less LM path at any size)
+  const bool want_tab = !(no_tab && atoi(no_tab) != 0);
+  if (want_tab && d.lm_type == JAMD_LM_NGRAM && cells > 0 && cells * sizeof(float) <= kIwTabMaxBytes) {
     // no room, or a build that failed: the kernels compute the entries on the fly, and the call has not failed, so
     // jamd_last_error() keeps what it said before
     const std::string said = jamd_last_error();
@@ -41,6 +43,11 @@ int jamd_lexicon_create(jamd_engine *e, const jamd_lexicon_desc *h, jamd_lexicon
   }
   *out = l.release();
   return JAMD_OK;
+}
+
+int jamd_lexicon_lm_table(const jamd_lexicon *l) {
+  if (!l) return -1;
+  return l->d.iwtab != nullptr ? 1 : 0;
 }
 
 void jamd_lexicon_destroy(jamd_lexicon *l) {

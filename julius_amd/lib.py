@@ -208,6 +208,7 @@ def load():
         "jamd_dnn_outprob_dev": (ci, [vp, vp, ci, vp, vp]),
         "jamd_dnn_outprob_host": (ci, [vp, vp, ci, vp]),
         "jamd_lexicon_create": (ci, [vp, vp, P(vp)]),
+        "jamd_lexicon_lm_table": (ci, [vp]),
         "jamd_lexicon_destroy": (None, [vp]),
         "jamd_beam_create": (ci, [vp, vp, ci, cf, ci, ci, P(vp)]),
         "jamd_beam_destroy": (None, [vp]),
@@ -741,6 +742,10 @@ class Lexicon:
             _check(load().jamd_lexicon_load(eng.h, str(path).encode(), C.byref(h)), "jamd_lexicon_load")
         self.h = h
         return self
+
+    def lm_table(self) -> int:
+        """1 = the cross-word LM table exists, 0 = the kernels compute its entries (jamd_lexicon_lm_table)."""
+        return load().jamd_lexicon_lm_table(self.h)
 
     def close(self):
         if getattr(self, "h", None):
