@@ -189,6 +189,70 @@ int  jamd_gmm_book_offsets(const jamd_gmm *g, int *off, int cap);
 int  jamd_gmm_dens_dev(jamd_gmm *g, const float *dev_frames, int T, float *dev_out, void *stream);
 int  jamd_gmm_dens_host(jamd_gmm *g, const float *host_frames, int T, float *host_out);
 
+/* ---------------------------------------------------- multi-stream GMM model */
+/* HTK_HMM_INFO of a model with opt.stream_info.num > 1 (`~o <StreamInfo> n v1 .. vn`), after outprob_init() has
+ * inverted the variances: what calc_mix() (libsent/src/phmm/calc_mix.c:41-81) walks for one state -- OP_nstream
+ * mixture pdfs, each over its own slice of the input vector (outprob.c:199-203), the streams' log-sums joined as
+ * sum_s weight[s] * logprob_s.  jamd_gmm_create() and its kin keep refusing nstream != 1; such a model has this
+ * object of its own.  A single-stream model (nstream = 1) is accepted too and scores as jamd_gmm does.
+ *   nstate, veclen   states (HTK_HMM_State.id order, htk_hmm.h:171-178) and opt.vec_size (htk_hmm.h:104)
+ *   nstream          opt.stream_info.num, 1 .. 50 (MAXSTREAMNUM, htk_defs.h:112; HTK_HMM_StreamInfo, htk_hmm.h:96-99)
+ *   vsize            [nstream] opt.stream_info.vsize[]; sums to veclen.  Stream s sees o[off_s .. off_s + vsize[s]),
+ *                    off_s = vsize[0] + .. + vsize[s - 1]
+ *   mixture pdfs     the pool of HTK_HMM_PDF (htk_hmm.h:157-165); a `~p` macro shared by several states is ONE pdf.
+ *                    pdf_stream[npdf]   stream_id (:160)
+ *                    pdf_off[npdf + 1]  the pdf's mixture entries in ent_dens / ent_logw (mix_num = the difference)
+ *                    pdf_book[npdf]     codebook id of a tied-mixture pdf (tmix, :159), -1 for a plain one; NULL = all
+ *                                       plain.  A tied-mixture pdf is refused (NOT SERVED below)
+ *   entries          ent_dens[nentry]   density index (b[i], :162), -1 for a NULL density
+ *                    ent_logw[nentry]   bweight[i] = ln w (:163, rdhmmdef_mpdf.c:189)
+ *   states           st_pdf[nstate][nstream]     pdf index of stream s (HTK_HMM_State.pdf[s], :175)
+ *                    st_weight[nstate][nstream]  stream weights (HTK_HMM_State.w->weight[s], :174, :142-147); 1.0 for
+ *                                                a state without <SWeights> (calc_mix.c:54-55); NULL = all 1.0
+ *   densities        HTK_HMM_Dens (:128-139) of DIFFERENT lengths: density g is as long as the stream that uses it
+ *                    dens_off[ndens + 1]  into mean / ivar (floats; length = the difference)
+ *                    mean, ivar           [dens_off[ndens]] values back to back; gconst[ndens]
+ * Arithmetic, bit for bit the reference's x86-64 object code: per Gaussian gconst, then for the slice's dimensions
+ * ascending four separately rounded fp32 operations, * -0.5 (LOG_ZERO for a NULL density), + ln w; addlog_array() from
+ * the pdf's last entry to its first; a stream at or below LOG_ZERO is skipped, any other adds logprob * weight (a
+ * rounded multiply, then a rounded add, from 0.0f); 0 or <= LOG_ZERO gives LOG_ZERO, anything else * INV_LOG_TEN.
+ * NOT SERVED (JAMD_EINVAL from jamd_gmm_ms_create): tied-mixture pdfs inside a stream (calc_tied_mix() per stream and
+ * its codebook cache), and gprune safe | heu | beam -- this object is `-gprune none` over plain mixtures. */
+typedef struct jamd_gmm_ms jamd_gmm_ms;
+typedef struct {
+  int nstate, veclen, nstream;
+  int npdf, nentry, ndens;
+  const int   *vsize;
+  const int   *pdf_stream;
+  const int   *pdf_off;
+  const int   *pdf_book;
+  const int   *ent_dens;
+  const float *ent_logw;
+  const int   *st_pdf;
+  const float *st_weight;
+  const int   *dens_off;
+  const float *mean, *ivar, *gconst;
+} jamd_gmm_ms_desc;
+
+/* Checks the whole description before the first device call (a refusal names the field and costs no upload), then
+ * packs every pdf's Gaussians in the order the kernel reads them and uploads once. */
+int  jamd_gmm_ms_create(jamd_engine *e, const jamd_gmm_ms_desc *d, jamd_gmm_ms **out);
+/* The same from the binary HMM definition mkbinhmm writes for such a model (read_binhmm.c: stream_info :261, the
+ * stream weights :445, stream_id per `~p` macro :588, nstream pdf ids and a weight id per state :633-690). */
+int  jamd_gmm_ms_load_binhmm(jamd_engine *e, const char *binhmm_path, jamd_gmm_ms **out);
+void jamd_gmm_ms_destroy(jamd_gmm_ms *g);
+int  jamd_gmm_ms_nstate(const jamd_gmm_ms *g);
+int  jamd_gmm_ms_veclen(const jamd_gmm_ms *g);
+int  jamd_gmm_ms_nstream(const jamd_gmm_ms *g);
+/* out[t][s] = log10 b_s(o_t) for frames [T][veclen] -> [T][nstate], both row-major: the matrix jamd_cdset_*,
+ * jamd_beam_pass1_dev() and jamd_beam_stream_push_dev() take.  The object keeps no device scratch that a call writes:
+ * calls on one jamd_gmm_ms may be in flight on several streams at once.  (_host stages through buffers the object
+ * owns and runs on the engine's own stream: one _host call at a time.) */
+int  jamd_gmm_ms_outprob_dev(jamd_gmm_ms *g, const float *dev_frames, int T, float *dev_out, void *stream);
+int  jamd_gmm_ms_outprob_host(jamd_gmm_ms *g, const float *host_frames, int T, float *host_out);
+/* Name and launch shape of the kernel the last outprob call used. */
+const char *jamd_gmm_ms_last_kernel(const jamd_gmm_ms *g);
+
 /* ---- Gaussian mixture selection (-gshmm FILE -gsnum N) --------------------------------------
  * Replaces gms_state() (libsent/src/phmm/gms.c:394-412, with compute_gs_scores()/do_gms(),
  * gms.c:189-264, and compute_g_max(), gms_gprune.c:80-150).  gs is the flattened selection model

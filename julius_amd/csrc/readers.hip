@@ -4,6 +4,9 @@
 //       (libsent/src/hmminfo/write_binhmm.c, read back by read_binhmm.c:756-903) -> the flat model of
 //       jamd_gmm_desc / the "JAMDGMM1" blob, byte for byte what jamd_export produces from the same file
 //       through Julius' own reader + julius_amd/shim/jamd_flatten.c (tests/test_readers.py compares the files).
+//   jamd_gmm_ms_load_binhmm()   the same file of a model of ANY stream count -> jamd_gmm_ms_desc: stream_info, the
+//       stream weight section, stream_id per `~p` macro, nstream pdf ids and a weight id per state
+//       (read_binhmm.c:261, :445, :588, :633-690).  The two entries above keep refusing nstream != 1.
 // Not covered: the tree lexicon and its LM tables.  The lexicon is not a file format but the output of
 // libjulius/src/wchmm.c (build_wchmm2(): 2 000 lines of tree building, cross-word context handling and factoring
 // set-up over the dictionary, the HMMList AND the LM -- the factoring values and the words kept out of the tree are
@@ -54,12 +57,20 @@ struct Reader {
   void skip(size_t bytes) { if (ok && bytes && fseek(f, (long)bytes, SEEK_CUR) != 0) ok = false; }
 };
 
-struct Pdf { bool tmix = false; int book = -1; std::vector<unsigned> dens; std::vector<float> w; };
+struct Pdf { bool tmix = false; int book = -1; int stream = 0; std::vector<unsigned> dens; std::vector<float> w; };
 
 struct FlatGmm {
   int S = 0, D = 0, G = 0, E = 0, nbook = 0;
   std::vector<float> mean, ivar, gconst, ent_logw;
   std::vector<int> st_off, ent_dens, st_book;
+};
+
+// A model of any stream count in the arrays of jamd_gmm_ms_desc: the file's pdfs and densities as they stand (ids are
+// file indices), nothing duplicated.
+struct FlatStreams {
+  int S = 0, D = 0, nstream = 0;
+  std::vector<int> vsize, pdf_stream, pdf_off, pdf_book, ent_dens, st_pdf, dens_off;
+  std::vector<float> ent_logw, st_weight, mean, ivar, gconst;
 };
 
 // rd_pdf_sub(), read_binhmm.c:544-585
@@ -80,7 +91,8 @@ bool read_pdf(Reader &r, Pdf &p, const std::vector<std::vector<unsigned>> &books
   return r.ok;
 }
 
-bool read_binhmm(const char *path, FlatGmm &out) {
+// ms == nullptr: a single-stream model into `out` (any other is refused); else a model of any stream count into *ms.
+bool read_binhmm(const char *path, FlatGmm &out, FlatStreams *ms = nullptr) {
   Reader r;
   if (!r.open(path)) return false;
   // rd_header(), read_binhmm.c:193-257
@@ -109,13 +121,16 @@ bool read_binhmm(const char *path, FlatGmm &out) {
   }
   // rd_opt() :261-271, rd_type() :280-285
   const short nstream = r.get<short>();
-  r.skip(2 * 50);                       // stream_info.vsize[MAXSTREAMNUM]
+  short vsize[50];                      // stream_info.vsize[MAXSTREAMNUM]
+  memset(vsize, 0, sizeof(vsize));
+  r.raw(vsize, 2, 50);
   const short vec_size = r.get<short>();
   r.skip(2 * 3);                        // cov_type, dur_type, param_type
   const unsigned char tied = r.get<unsigned char>();
   r.skip(4);                            // maxmixturenum
   if (!r.ok) return false;
-  if (nstream != 1) { jamd_set_error("%s: %d streams (the device path serves single-stream models)", path, (int)nstream); return false; }
+  if (!ms && nstream != 1) { jamd_set_error("%s: %d streams (the device path serves single-stream models)", path, (int)nstream); return false; }
+  if (nstream < 1 || nstream > 50) { jamd_set_error("%s: %d streams", path, (int)nstream); return false; }
   const int D = vec_size;
   // rd_trans() :303-341: not part of the state pool
   const unsigned ntr = r.get<unsigned>();
@@ -148,6 +163,20 @@ bool read_binhmm(const char *path, FlatGmm &out) {
     dens[i].gconst = r.get<float>();
     if (r.ok && dens[i].var >= nvar) { jamd_set_error("%s: variance id out of range", path); return false; }
   }
+  // rd_streamweight() :445-470, only in a file of more than one stream
+  std::vector<std::vector<float>> sweight;
+  if (nstream > 1) {
+    const unsigned nsw = r.get<unsigned>();
+    if (!r.ok || nsw > (1u << 24)) { jamd_set_error("%s: bad stream weight count", path); return false; }
+    sweight.resize(nsw);
+    for (unsigned i = 0; r.ok && i < nsw; i++) {
+      r.str();
+      const short len = r.get<short>();
+      if (len < 0) { r.ok = false; break; }
+      sweight[i].resize((size_t)len);
+      r.raw(sweight[i].data(), 4, (size_t)len);
+    }
+  }
   // rd_tmix() :489-527
   std::vector<std::vector<unsigned>> books;
   if (tied) {
@@ -168,21 +197,62 @@ bool read_binhmm(const char *path, FlatGmm &out) {
     const unsigned n = r.get<unsigned>();
     if (!r.ok || n > (1u << 28)) { jamd_set_error("%s: bad mixture pdf count", path); return false; }
     mpdf.resize(n);
-    for (unsigned i = 0; r.ok && i < n; i++) { r.str(); r.skip(2); if (!read_pdf(r, mpdf[i], books)) return false; }
+    for (unsigned i = 0; r.ok && i < n; i++) { r.str(); mpdf[i].stream = r.get<short>(); if (!read_pdf(r, mpdf[i], books)) return false; }
   }
   // rd_state() :633-697: a state's id is its index in the file
   const unsigned nst = r.get<unsigned>();
   if (!r.ok || nst == 0 || nst > (1u << 28)) { jamd_set_error("%s: bad state count", path); return false; }
-  std::vector<Pdf> st(nst);
+  std::vector<Pdf> st(ms ? 0 : nst);
+  std::vector<unsigned> st_swid;         // (more than one stream) a state's stream weight id, >= the count: none
   for (unsigned i = 0; r.ok && i < nst; i++) {
     r.str();
-    if (mpdf_macro) {
-      const unsigned mid = r.get<unsigned>();
-      if (!r.ok || mid >= mpdf.size()) { jamd_set_error("%s: state %u without a mixture pdf", path, i); return false; }
-      st[i] = mpdf[mid];
-    } else if (!read_pdf(r, st[i], books)) return false;
+    for (int m = 0; r.ok && m < nstream; m++) {
+      if (mpdf_macro) {
+        const unsigned mid = r.get<unsigned>();
+        if (!r.ok || mid >= mpdf.size()) { jamd_set_error("%s: state %u without a mixture pdf", path, i); return false; }
+        if (ms) ms->st_pdf.push_back((int)mid); else st[i] = mpdf[mid];
+      } else if (ms) {                   // in-line pdfs join the pool in file order; stream_id = the slot (:669)
+        if (mpdf.size() > (1u << 28)) { r.ok = false; break; }
+        mpdf.emplace_back();
+        mpdf.back().stream = m;
+        if (!read_pdf(r, mpdf.back(), books)) return false;
+        ms->st_pdf.push_back((int)mpdf.size() - 1);
+      } else if (!read_pdf(r, st[i], books)) return false;
+    }
+    if (nstream > 1) st_swid.push_back(r.get<unsigned>());
   }
   if (!r.ok) return false;
+  if (ms) {
+    ms->S = (int)nst; ms->D = D; ms->nstream = nstream;
+    ms->vsize.assign(vsize, vsize + nstream);
+    ms->dens_off.assign(1, 0);
+    for (unsigned g = 0; g < ndens; g++) {
+      const std::vector<float> &v = var[dens[g].var];
+      if (v.size() != dens[g].mean.size()) { jamd_set_error("%s: density %u: mean and variance differ in length", path, g); return false; }
+      ms->mean.insert(ms->mean.end(), dens[g].mean.begin(), dens[g].mean.end());
+      ms->ivar.insert(ms->ivar.end(), v.begin(), v.end());
+      ms->gconst.push_back(dens[g].gconst);
+      ms->dens_off.push_back((int)ms->mean.size());
+    }
+    ms->pdf_off.assign(1, 0);
+    for (const Pdf &p : mpdf) {
+      ms->pdf_stream.push_back(p.stream);
+      ms->pdf_book.push_back(p.tmix ? p.book : -1);
+      for (size_t i = 0; i < p.dens.size(); i++) {
+        ms->ent_dens.push_back(p.dens[i] < ndens ? (int)p.dens[i] : -1);   // an id >= dens_num: a NULL density (:561-565)
+        ms->ent_logw.push_back(p.w[i]);
+      }
+      ms->pdf_off.push_back((int)ms->ent_dens.size());
+    }
+    ms->st_weight.assign((size_t)nst * nstream, 1.0f);                     // no weight macro: 1.0 (calc_mix.c:54-55)
+    for (unsigned i = 0; i < nst && nstream > 1; i++) {
+      if (st_swid[i] >= sweight.size()) continue;
+      const std::vector<float> &w = sweight[st_swid[i]];
+      if ((int)w.size() != nstream) { jamd_set_error("%s: state %u: %zu stream weights for %d streams", path, i, w.size(), (int)nstream); return false; }
+      for (int m = 0; m < nstream; m++) ms->st_weight[(size_t)i * nstream + m] = w[(size_t)m];
+    }
+    return true;
+  }
 
   // the walk of julius_amd/shim/jamd_flatten.c over hmminfo->ststart: state_add() prepends (rdhmmdef_state.c:67-68),
   // so the list runs from the LAST state of the file to the first; densities are numbered at first sight
@@ -356,6 +426,22 @@ int jamd_gmm_load_binhmm(jamd_engine *e, const char *binhmm_path, int gprune, in
   d.mean = g.mean.data(); d.ivar = g.ivar.data(); d.gconst = g.gconst.data(); d.st_off = g.st_off.data();
   d.ent_dens = g.ent_dens.data(); d.ent_logw = g.ent_logw.data(); d.st_book = g.st_book.data();
   return jamd_gmm_create(e, &d, gprune, gprune_num, out);
+}
+
+int jamd_gmm_ms_load_binhmm(jamd_engine *e, const char *binhmm_path, jamd_gmm_ms **out) {
+  if (!e || !binhmm_path || !out) { jamd_set_error("jamd_gmm_ms_load_binhmm: NULL argument"); return JAMD_EINVAL; }
+  *out = nullptr;
+  FlatGmm unused;
+  FlatStreams g;
+  if (!read_binhmm(binhmm_path, unused, &g)) return JAMD_EINVAL;
+  jamd_gmm_ms_desc d;
+  memset(&d, 0, sizeof(d));
+  d.nstate = g.S; d.veclen = g.D; d.nstream = g.nstream;
+  d.npdf = (int)g.pdf_stream.size(); d.nentry = (int)g.ent_dens.size(); d.ndens = (int)g.gconst.size();
+  d.vsize = g.vsize.data(); d.pdf_stream = g.pdf_stream.data(); d.pdf_off = g.pdf_off.data(); d.pdf_book = g.pdf_book.data();
+  d.ent_dens = g.ent_dens.data(); d.ent_logw = g.ent_logw.data(); d.st_pdf = g.st_pdf.data(); d.st_weight = g.st_weight.data();
+  d.dens_off = g.dens_off.data(); d.mean = g.mean.data(); d.ivar = g.ivar.data(); d.gconst = g.gconst.data();
+  return jamd_gmm_ms_create(e, &d, out);
 }
 
 }  // extern "C"

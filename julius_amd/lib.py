@@ -36,6 +36,12 @@ class GmmDesc(C.Structure):
     ]
 
 
+class GmmStreamsDesc(C.Structure):
+    """jamd_gmm_ms_desc (include/julius_amd.h): a multi-stream model's pdf pool, states and densities."""
+    _fields_ = [(n, C.c_int) for n in ("nstate", "veclen", "nstream", "npdf", "nentry", "ndens")] + [
+        (n, C.c_void_p) for n in ("vsize", "pdf_stream", "pdf_off", "pdf_book", "ent_dens", "ent_logw", "st_pdf",
+                                  "st_weight", "dens_off", "mean", "ivar", "gconst")]
+
 
 class DnnDesc(C.Structure):
     _fields_ = [
@@ -161,6 +167,15 @@ def load():
         "jamd_gmm_book_offsets": (ci, [vp, vp, ci]),
         "jamd_gmm_dens_dev": (ci, [vp, vp, ci, vp, vp]),
         "jamd_gmm_dens_host": (ci, [vp, vp, ci, vp]),
+        "jamd_gmm_ms_create": (ci, [vp, P(GmmStreamsDesc), P(vp)]),
+        "jamd_gmm_ms_load_binhmm": (ci, [vp, C.c_char_p, P(vp)]),
+        "jamd_gmm_ms_destroy": (None, [vp]),
+        "jamd_gmm_ms_nstate": (ci, [vp]),
+        "jamd_gmm_ms_veclen": (ci, [vp]),
+        "jamd_gmm_ms_nstream": (ci, [vp]),
+        "jamd_gmm_ms_outprob_dev": (ci, [vp, vp, ci, vp, vp]),
+        "jamd_gmm_ms_outprob_host": (ci, [vp, vp, ci, vp]),
+        "jamd_gmm_ms_last_kernel": (C.c_char_p, [vp]),
         "jamd_gms_create": (ci, [vp, P(GmmDesc), vp, ci, ci, P(vp)]),
         "jamd_gms_destroy": (None, [vp]),
         "jamd_gms_load": (ci, [vp, C.c_char_p, P(vp)]),
@@ -493,6 +508,81 @@ class Gmm:
             self.close()
         except Exception:
             pass
+
+class GmmStreams:
+    """Device-resident multi-stream GMM acoustic model (jamd_gmm_ms): per-state stream weights over a pool of
+    mixture pdfs, `-gprune none`.  model: nstream, vsize[nstream], pdf_stream[npdf], pdf_off[npdf + 1],
+    ent_dens / ent_logw[nentry], st_pdf[S][nstream], st_weight[S][nstream] or None, dens_off[ndens + 1],
+    mean / ivar (flat, back to back), gconst[ndens]; pdf_book[npdf] optional."""
+
+    _INT = ("vsize", "pdf_stream", "pdf_off", "ent_dens", "st_pdf", "dens_off")
+    _FLT = ("ent_logw", "mean", "ivar", "gconst")
+
+    @classmethod
+    def make_desc(cls, model: dict):
+        """(GmmStreamsDesc, the arrays it points into)."""
+        keep = {k: _i32(model[k]) for k in cls._INT}
+        keep.update({k: _f32(model[k]).reshape(-1) for k in cls._FLT})
+        keep["st_pdf"] = keep["st_pdf"].reshape(-1, len(keep["vsize"]))
+        for k, conv in (("st_weight", _f32), ("pdf_book", _i32)):
+            if model.get(k) is not None:
+                keep[k] = conv(model[k])
+        d = GmmStreamsDesc()
+        d.nstate = keep["st_pdf"].shape[0]
+        d.veclen = int(model["veclen"]) if "veclen" in model else int(keep["vsize"].sum())
+        d.nstream = int(model.get("nstream", len(keep["vsize"])))
+        d.npdf, d.nentry, d.ndens = len(keep["pdf_stream"]), len(keep["ent_dens"]), len(keep["gconst"])
+        for k in cls._INT + cls._FLT + ("st_weight", "pdf_book"):
+            setattr(d, k, keep[k].ctypes.data if k in keep else None)
+        return d, keep
+
+    def __init__(self, eng: Engine, model: dict):
+        self.eng = eng
+        d, self._keep = self.make_desc(model)
+        h = C.c_void_p()
+        _check(load().jamd_gmm_ms_create(eng.h, C.byref(d), C.byref(h)), "jamd_gmm_ms_create")
+        self._adopt(h)
+
+    def _adopt(self, h):
+        lib = load()
+        self.h = h
+        self.S, self.D, self.nstream = lib.jamd_gmm_ms_nstate(h), lib.jamd_gmm_ms_veclen(h), lib.jamd_gmm_ms_nstream(h)
+
+    @classmethod
+    def from_binhmm(cls, eng: Engine, path):
+        """jamd_gmm_ms_load_binhmm(): mkbinhmm's file of a model of any stream count, read by the library itself."""
+        self = cls.__new__(cls)
+        self.eng, self._keep = eng, {}
+        h = C.c_void_p()
+        _check(load().jamd_gmm_ms_load_binhmm(eng.h, str(path).encode(), C.byref(h)), "jamd_gmm_ms_load_binhmm")
+        self._adopt(h)
+        return self
+
+    def outprob_host(self, frames: np.ndarray) -> np.ndarray:
+        fr = _f32(frames)
+        T = fr.shape[0]
+        assert fr.ndim == 2 and fr.shape[1] == self.D
+        out = np.empty((T, self.S), dtype=np.float32)
+        _check(load().jamd_gmm_ms_outprob_host(self.h, fr.ctypes.data, T, out.ctypes.data), "jamd_gmm_ms_outprob_host")
+        return out
+
+    def outprob_dev(self, dev_frames: int, T: int, dev_out: int, stream: int = 0):
+        _check(load().jamd_gmm_ms_outprob_dev(self.h, dev_frames, T, dev_out, stream or None), "jamd_gmm_ms_outprob_dev")
+
+    def last_kernel(self) -> str:
+        return load().jamd_gmm_ms_last_kernel(self.h).decode()
+
+    def close(self):
+        if getattr(self, "h", None):
+            load().jamd_gmm_ms_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
 
 class Gms:
     """Gaussian mixture selection stage (jamd_gms): gms_state() of libsent/src/phmm/gms.c."""
