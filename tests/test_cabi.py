@@ -16,6 +16,77 @@ def test_library_loads_and_exports_declared_symbols():
     assert l.jamd_abi_version() == 4
 
 
+def test_signature_table_names_every_declared_function():
+    """Every function of the header has its restype / argtypes: one called without them would pass pointers as C int."""
+    assert sorted(lib.SIGNATURES) == lib.declared_symbols()
+
+
+def _header_param_counts():
+    import re
+    hdr = (lib._PKG.parent / "include" / "julius_amd.h").read_text()
+    hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
+    hdr = re.sub(r"//[^\n]*", "", hdr)
+    counts = {}
+    for name, params in re.findall(r"\b(jamd_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", hdr):
+        params = params.strip()
+        assert name not in counts, f"{name} is declared twice"
+        counts[name] = 0 if params in ("", "void") else len(params.split(","))
+    return counts
+
+
+def test_signature_table_has_the_headers_parameter_counts():
+    counts = _header_param_counts()
+    assert sorted(counts) == lib.declared_symbols()
+    wrong = {n: (len(args), counts[n]) for n, (_, args) in lib.SIGNATURES.items() if len(args) != counts[n]}
+    assert not wrong, f"argtypes / header parameters: {wrong}"
+
+
+def _mirrors():
+    from julius_amd import lexblob
+    return {"jamd_gmm_desc": lib.GmmDesc, "jamd_gmm_ms_desc": lib.GmmStreamsDesc, "jamd_dnn_desc": lib.DnnDesc,
+            "jamd_lexicon_desc": lexblob.LexiconDesc, "jamd_trellis_atom": lexblob.TrellisAtom,
+            "jamd_pass1_result": lib.Pass1Result, "jamd_frontend_desc": lib.FrontendDesc,
+            "jamd_frontend_ss": lib.FrontendSS, "jamd_frontend_live_desc": lib.FrontendLiveDesc,
+            "jamd_adin_desc": lib.AdinDesc, "jamd_adin_cut_desc": lib.AdinCutDesc, "jamd_fvad_model": lib.FvadModel,
+            "jamd_fvad_desc": lib.FvadDesc, "jamd_adin_cut_fvad": lib.AdinCutFvad}
+
+
+def test_struct_mirrors_have_the_headers_layout(tmp_path):
+    """sizeof and every field's offsetof and size, as gcc lays the header's structs out, against the ctypes mirrors."""
+    import ctypes as C
+    from julius_amd import lexblob
+    mirrors = _mirrors()
+    structs = [v for m in (lib, lexblob) for v in vars(m).values()
+               if isinstance(v, type) and issubclass(v, C.Structure) and v is not C.Structure]
+    assert len(mirrors) == 14 and set(mirrors.values()) == set(structs), "a struct mirror is not checked"
+    body, want = [], []
+    for ctype, cls in mirrors.items():
+        body.append(f'  printf("{ctype} %zu\\n", sizeof({ctype}));')
+        want.append(f"{ctype} {C.sizeof(cls)}")
+        for f, _ in cls._fields_:
+            body.append(f'  printf("{ctype}.{f} %zu %zu\\n", offsetof({ctype}, {f}), sizeof((({ctype} *)0)->{f}));')
+            want.append(f"{ctype}.{f} {getattr(cls, f).offset} {getattr(cls, f).size}")
+    src = tmp_path / "layout.c"
+    src.write_text('#include <stddef.h>\n#include <stdio.h>\n#include "julius_amd.h"\nint main(void) {\n'
+                   + "\n".join(body) + "\n  return 0;\n}\n")
+    subprocess.run(["gcc", "-std=c99", "-Wall", "-Werror", "-I", str(lib._PKG.parent / "include"),
+                    str(src), "-o", str(tmp_path / "layout")], check=True)
+    got = subprocess.run([str(tmp_path / "layout")], check=True, capture_output=True, text=True).stdout.splitlines()
+    assert got == want, [(g, w) for g, w in zip(got, want) if g != w]
+
+
+def test_atom_dtype_is_the_trellis_atom():
+    import ctypes as C
+    from julius_amd import lexblob
+    dt, atom = lexblob.ATOM_DTYPE, lexblob.TrellisAtom
+    assert list(dt.names) == [f for f, _ in atom._fields_]
+    assert dt.itemsize == C.sizeof(atom)
+    for f, ctype in atom._fields_:
+        sub, off = dt.fields[f][:2]
+        assert (off, sub.itemsize) == (getattr(atom, f).offset, getattr(atom, f).size), f
+        assert sub.kind == ("f" if ctype is C.c_float else "i"), f
+
+
 def test_header_is_plain_c(tmp_path):
     src = tmp_path / "t.c"
     src.write_text('#include "julius_amd.h"\nint main(void){return JAMD_ABI_VERSION-1;}\n')
