@@ -203,7 +203,11 @@ int  jamd_gmm_dens_host(jamd_gmm *g, const float *host_frames, int T, float *hos
  *                    pdf_stream[npdf]   stream_id (:160)
  *                    pdf_off[npdf + 1]  the pdf's mixture entries in ent_dens / ent_logw (mix_num = the difference)
  *                    pdf_book[npdf]     codebook id of a tied-mixture pdf (tmix, :159), -1 for a plain one; NULL = all
- *                                       plain.  A tied-mixture pdf is refused (NOT SERVED below)
+ *                                       plain.  The ids are dense, 0 .. nbook - 1 (GCODEBOOK.id).  The entries of a
+ *                                       tied-mixture pdf name its codebook's densities d[0 .. num) in order (-1 for a
+ *                                       member the file leaves undefined) and carry its bweight: every pdf of a book
+ *                                       lists the same ent_dens and has the same pdf_stream.  jamd_gmm_ms_create()
+ *                                       refuses a tied-mixture pdf; jamd_gmm_ms_create_opt() serves it
  *   entries          ent_dens[nentry]   density index (b[i], :162), -1 for a NULL density
  *                    ent_logw[nentry]   bweight[i] = ln w (:163, rdhmmdef_mpdf.c:189)
  *   states           st_pdf[nstate][nstream]     pdf index of stream s (HTK_HMM_State.pdf[s], :175)
@@ -216,8 +220,10 @@ int  jamd_gmm_dens_host(jamd_gmm *g, const float *host_frames, int T, float *hos
  * ascending four separately rounded fp32 operations, * -0.5 (LOG_ZERO for a NULL density), + ln w; addlog_array() from
  * the pdf's last entry to its first; a stream at or below LOG_ZERO is skipped, any other adds logprob * weight (a
  * rounded multiply, then a rounded add, from 0.0f); 0 or <= LOG_ZERO gives LOG_ZERO, anything else * INV_LOG_TEN.
- * NOT SERVED (JAMD_EINVAL from jamd_gmm_ms_create): tied-mixture pdfs inside a stream (calc_tied_mix() per stream and
- * its codebook cache), and gprune safe | heu | beam -- this object is `-gprune none` over plain mixtures. */
+ * jamd_gmm_ms_create() is `-gprune none` over plain mixtures; tied-mixture codebooks and `-gprune safe` are
+ * jamd_gmm_ms_create_opt()'s (below).
+ * NOT SERVED (JAMD_EINVAL): gprune heu | beam for multi-stream objects; multi-stream models at the shim / plugin
+ * boundaries (jamd_flatten_hmminfo() refuses them, julius_amd/shim/jamd_flatten.c:109); MSD. */
 typedef struct jamd_gmm_ms jamd_gmm_ms;
 typedef struct {
   int nstate, veclen, nstream;
@@ -245,13 +251,47 @@ int  jamd_gmm_ms_nstate(const jamd_gmm_ms *g);
 int  jamd_gmm_ms_veclen(const jamd_gmm_ms *g);
 int  jamd_gmm_ms_nstream(const jamd_gmm_ms *g);
 /* out[t][s] = log10 b_s(o_t) for frames [T][veclen] -> [T][nstate], both row-major: the matrix jamd_cdset_*,
- * jamd_beam_pass1_dev() and jamd_beam_stream_push_dev() take.  The object keeps no device scratch that a call writes:
- * calls on one jamd_gmm_ms may be in flight on several streams at once.  (_host stages through buffers the object
+ * jamd_beam_pass1_dev() and jamd_beam_stream_push_dev() take.  An object made by jamd_gmm_ms_create() keeps no device scratch that a
+ * call writes: calls on it may be in flight on several streams at once (for jamd_gmm_ms_create_opt()'s see there).  (_host stages through buffers the object
  * owns and runs on the engine's own stream: one _host call at a time.) */
 int  jamd_gmm_ms_outprob_dev(jamd_gmm_ms *g, const float *dev_frames, int T, float *dev_out, void *stream);
 int  jamd_gmm_ms_outprob_host(jamd_gmm_ms *g, const float *host_frames, int T, float *host_out);
 /* Name and launch shape of the kernel the last outprob call used. */
 const char *jamd_gmm_ms_last_kernel(const jamd_gmm_ms *g);
+
+/* The same object for a model with tied-mixture codebooks (calc_tied_mix() / calc_compound_mix()'s stream loops over
+ * the per-(frame, codebook) cache, libsent/src/phmm/calc_tied_mix.c:177-236, :274-345), and for any multi-stream model
+ * under `-gprune safe`.
+ *   gprune        JAMD_GPRUNE_NONE or JAMD_GPRUNE_SAFE; HEU and BEAM are refused by name
+ *   gprune_num    OP_gprune_num (-tmix); ignored for NONE, 1 .. 64 for SAFE as jamd_gmm_create()
+ *   chunk_frames  0, or the frames the object's device scratch covers at a time.  0 = 2048, or as many fewer (in steps
+ *                 of 128, at least 128) as keep the scratch within 256 MiB.  Results do not depend on it.
+ * The scratch -- the cache [books][cap][chunk_frames + 1] of (score, id) and [books][chunk_frames + 1] of (num, mark);
+ * under SAFE every plain pdf has a column of its own beside the codebooks' -- is allocated ONCE, here; an outprob call
+ * walks its frames chunk by chunk on the caller's stream and neither allocates nor waits for the device.  So an object
+ * with a tied-mixture pdf, or under SAFE, serves ONE call at a time (queue calls on one stream, or use one object per
+ * stream); a model of plain pdfs under NONE is exactly what jamd_gmm_ms_create() makes, several streams at once
+ * included.  Arithmetic as above, with calc_tied_mix()'s `score + bweight[id]` (one rounded add) over the cached
+ * slots, log-summed from the last slot down. */
+typedef struct { int gprune; int gprune_num; int chunk_frames; } jamd_gmm_ms_opt;
+int  jamd_gmm_ms_create_opt(jamd_engine *e, const jamd_gmm_ms_desc *d, const jamd_gmm_ms_opt *opt, jamd_gmm_ms **out);
+/* ... from the binary HMM definition: rd_tmix()'s codebook section and the tmix form of a pdf (read_binhmm.c:489-567). */
+int  jamd_gmm_ms_load_binhmm_opt(jamd_engine *e, const char *binhmm_path, const jamd_gmm_ms_opt *opt, jamd_gmm_ms **out);
+/* A BATCH of utterances laid back to back, utt_off a HOST array of nutt + 1 ints with utt_off[0] = 0 (as
+ * jamd_gmm_outprob_utts_dev()).  The boundaries matter only under SAFE with tied-mixture pdfs: an utterance's first
+ * frame has no history (calc_tied_mix.c:203-215; outprob_prepare() clears the cache).  jamd_gmm_ms_outprob_dev() /
+ * _host() treat their T frames as one utterance. */
+int  jamd_gmm_ms_outprob_utts_dev(jamd_gmm_ms *g, const float *dev_frames, const int *utt_off, int nutt, float *dev_out,
+                                  void *stream);
+int  jamd_gmm_ms_outprob_utts_host(jamd_gmm_ms *g, const float *host_frames, const int *utt_off, int nutt, float *host_out);
+/* Cache slots per (frame, codebook) -- the largest codebook for NONE, min(gprune_num, the largest mixture or
+ * codebook) for SAFE; 0 without a tied-mixture pdf -- and the codebook count. */
+int  jamd_gmm_ms_tmix_cap(const jamd_gmm_ms *g);
+int  jamd_gmm_ms_nbook(const jamd_gmm_ms *g);
+/* The codebook cache for inspection, as jamd_gmm_tmix_cache_dev(): dev_score / dev_id [T][nbook][cap], dev_num
+ * [T][nbook]; T frames of one utterance. */
+int  jamd_gmm_ms_tmix_cache_dev(jamd_gmm_ms *g, const float *dev_frames, int T, float *dev_score, int *dev_id, int *dev_num,
+                                void *stream);
 
 /* ---- Gaussian mixture selection (-gshmm FILE -gsnum N) --------------------------------------
  * Replaces gms_state() (libsent/src/phmm/gms.c:394-412, with compute_gs_scores()/do_gms(),

@@ -193,4 +193,27 @@ static inline int dispatch_topn(int cap, F &&f) {
   return f(std::integral_constant<int, 64>{});
 }
 
+// The same list held by a WAVE, for the kernels in which one wave walks a codebook's frames in order (the history
+// forms of gmm_pruned.hip, the order pass of gmm_ms_tied.hip).
+struct TopList {                 // lane p holds entry p of the descending list (cap <= 64)
+  float sc; int id; int len, cap;
+  __device__ __forceinline__ void push(float score, int gid, int lane) {      // cache_push(), gprune_common.c:88-126
+    const float last = __shfl(sc, len > 0 ? len - 1 : 0, 64);
+    if (len > 0 && last >= score) {                                            // bottom: append if there is room
+      if (len < cap) { if (lane == len) { sc = score; id = gid; } len++; }
+      return;
+    }
+    const int p = __popcll(__ballot(lane < len && sc > score));                // entries strictly greater stay in front
+    const float usc = __shfl_up(sc, 1, 64); const int uid = __shfl_up(id, 1, 64);
+    if (lane > p && lane <= len && lane < cap) { sc = usc; id = uid; }
+    if (lane == p) { sc = score; id = gid; }
+    if (len < cap) len++;
+  }
+  // the branch without history: compute_g_safe()'s LOG_ZERO for a Gaussian below a full list's last entry (topn_push_safe())
+  __device__ __forceinline__ void push_safe(float score, int gid, int lane) {
+    if (len == cap && score < __shfl(sc, cap - 1, 64)) score = JAMD_LOG_ZERO;
+    push(score, gid, lane);
+  }
+};
+
 }  // namespace jamd

@@ -160,26 +160,7 @@ tmix_book_kernel(const float *__restrict__ brec, const int *__restrict__ book_of
 //      entry per lane.
 // Frame 0 of an utterance (and a frame whose predecessor cached nothing) takes the safe-pruning branch (:337-350) =
 // compute_g_base() scores pushed in index order.  Same MIXCACHE layout as tmix_book_kernel.
-struct TopList {                 // lane p holds entry p of the descending list (cap <= 64)
-  float sc; int id; int len, cap;
-  __device__ __forceinline__ void push(float score, int gid, int lane) {      // cache_push(), gprune_common.c:88-126
-    const float last = __shfl(sc, len > 0 ? len - 1 : 0, 64);
-    if (len > 0 && last >= score) {                                            // bottom: append if there is room
-      if (len < cap) { if (lane == len) { sc = score; id = gid; } len++; }
-      return;
-    }
-    const int p = __popcll(__ballot(lane < len && sc > score));                // entries strictly greater stay in front
-    const float usc = __shfl_up(sc, 1, 64); const int uid = __shfl_up(id, 1, 64);
-    if (lane > p && lane <= len && lane < cap) { sc = usc; id = uid; }
-    if (lane == p) { sc = score; id = gid; }
-    if (len < cap) len++;
-  }
-  // the branch without history: compute_g_safe()'s LOG_ZERO for a Gaussian below a full list's last entry (topn_push_safe(), gmm_dev.h)
-  __device__ __forceinline__ void push_safe(float score, int gid, int lane) {
-    if (len == cap && score < __shfl(sc, cap - 1, 64)) score = JAMD_LOG_ZERO;
-    push(score, gid, lane);
-  }
-};
+// (TopList, the list with one entry per lane: gmm_dev.h)
 
 template <int METHOD>
 __global__ void __launch_bounds__(64)

@@ -428,8 +428,9 @@ int jamd_gmm_load_binhmm(jamd_engine *e, const char *binhmm_path, int gprune, in
   return jamd_gmm_create(e, &d, gprune, gprune_num, out);
 }
 
-int jamd_gmm_ms_load_binhmm(jamd_engine *e, const char *binhmm_path, jamd_gmm_ms **out) {
-  if (!e || !binhmm_path || !out) { jamd_set_error("jamd_gmm_ms_load_binhmm: NULL argument"); return JAMD_EINVAL; }
+// opt == nullptr: jamd_gmm_ms_load_binhmm()
+static int ms_load_binhmm(const char *who, jamd_engine *e, const char *binhmm_path, const jamd_gmm_ms_opt *opt, jamd_gmm_ms **out) {
+  if (!e || !binhmm_path || !out) { jamd_set_error("%s: NULL argument", who); return JAMD_EINVAL; }
   *out = nullptr;
   FlatGmm unused;
   FlatStreams g;
@@ -441,7 +442,19 @@ int jamd_gmm_ms_load_binhmm(jamd_engine *e, const char *binhmm_path, jamd_gmm_ms
   d.vsize = g.vsize.data(); d.pdf_stream = g.pdf_stream.data(); d.pdf_off = g.pdf_off.data(); d.pdf_book = g.pdf_book.data();
   d.ent_dens = g.ent_dens.data(); d.ent_logw = g.ent_logw.data(); d.st_pdf = g.st_pdf.data(); d.st_weight = g.st_weight.data();
   d.dens_off = g.dens_off.data(); d.mean = g.mean.data(); d.ivar = g.ivar.data(); d.gconst = g.gconst.data();
-  return jamd_gmm_ms_create(e, &d, out);
+  return opt ? jamd_gmm_ms_create_opt(e, &d, opt, out) : jamd_gmm_ms_create(e, &d, out);
+}
+
+int jamd_gmm_ms_load_binhmm(jamd_engine *e, const char *binhmm_path, jamd_gmm_ms **out) {
+  return ms_load_binhmm("jamd_gmm_ms_load_binhmm", e, binhmm_path, nullptr, out);
+}
+
+// The same file under the options of jamd_gmm_ms_create_opt(): rd_tmix()'s codebooks and the tmix form of a pdf
+// (read_binhmm.c:489-567) arrive as pdf_book / the book's member list per pdf.
+int jamd_gmm_ms_load_binhmm_opt(jamd_engine *e, const char *binhmm_path, const jamd_gmm_ms_opt *opt, jamd_gmm_ms **out) {
+  if (out) *out = nullptr;
+  if (!opt) { jamd_set_error("jamd_gmm_ms_load_binhmm_opt: opt is NULL"); return JAMD_EINVAL; }
+  return ms_load_binhmm("jamd_gmm_ms_load_binhmm_opt", e, binhmm_path, opt, out);
 }
 
 }  // extern "C"

@@ -188,6 +188,13 @@ def _signatures():
         "jamd_gmm_ms_outprob_dev": (ci, [vp, vp, ci, vp, vp]),
         "jamd_gmm_ms_outprob_host": (ci, [vp, vp, ci, vp]),
         "jamd_gmm_ms_last_kernel": (cs, [vp]),
+        "jamd_gmm_ms_create_opt": (ci, [vp, P(GmmStreamsDesc), vp, P(vp)]),
+        "jamd_gmm_ms_load_binhmm_opt": (ci, [vp, cs, vp, P(vp)]),
+        "jamd_gmm_ms_outprob_utts_dev": (ci, [vp, vp, vp, ci, vp, vp]),
+        "jamd_gmm_ms_outprob_utts_host": (ci, [vp, vp, vp, ci, vp]),
+        "jamd_gmm_ms_tmix_cap": (ci, [vp]),
+        "jamd_gmm_ms_nbook": (ci, [vp]),
+        "jamd_gmm_ms_tmix_cache_dev": (ci, [vp, vp, ci, vp, vp, vp, vp]),
         # Gaussian mixture selection
         "jamd_gms_create": (ci, [vp, P(GmmDesc), vp, ci, ci, P(vp)]),
         "jamd_gms_load": (ci, [vp, cs, P(vp)]),
@@ -581,7 +588,7 @@ class Gmm(_Handle):
 
 class GmmStreams(_Handle):
     """Device-resident multi-stream GMM acoustic model (jamd_gmm_ms): per-state stream weights over a pool of
-    mixture pdfs, `-gprune none`.  model: nstream, vsize[nstream], pdf_stream[npdf], pdf_off[npdf + 1],
+    mixture pdfs, `-gprune none` (tied-mixture pdfs and `-gprune safe`: GmmStreamsTied).  model: nstream, vsize[nstream], pdf_stream[npdf], pdf_off[npdf + 1],
     ent_dens / ent_logw[nentry], st_pdf[S][nstream], st_weight[S][nstream] or None, dens_off[ndens + 1],
     mean / ivar (flat, back to back), gconst[ndens]; pdf_book[npdf] optional."""
     _destroy = "jamd_gmm_ms_destroy"
@@ -635,6 +642,68 @@ class GmmStreams(_Handle):
 
     def last_kernel(self) -> str:
         return load().jamd_gmm_ms_last_kernel(self.h).decode()
+
+    def outprob_utts_dev(self, dev_frames: int, utt_off, dev_out: int, stream: int = 0):
+        """A batch of utterances back to back (the boundaries matter to gprune safe over tied-mixture pdfs)."""
+        off = _i32(utt_off)
+        _call("jamd_gmm_ms_outprob_utts_dev", self.h, dev_frames, off.ctypes.data, len(off) - 1, dev_out, stream or None)
+
+
+class GmmStreamsTied(GmmStreams):
+    """jamd_gmm_ms through jamd_gmm_ms_create_opt(): tied-mixture codebooks (model["pdf_book"]) and `-gprune safe`.
+    GmmStreams with the keyword arguments gprune = None | "none" | "safe", gprune_num (-tmix) and chunk_frames; None
+    routes to the entries GmmStreams itself uses.  (A class of its own: GmmStreams' signatures are a kept surface.)"""
+
+    class Opt(C.Structure):
+        """jamd_gmm_ms_opt (include/julius_amd.h)."""
+        _fields_ = [("gprune", C.c_int), ("gprune_num", C.c_int), ("chunk_frames", C.c_int)]
+
+    _GPRUNE = {"none": GPRUNE_NONE, "safe": GPRUNE_SAFE, "heu": GPRUNE_HEU, "beam": GPRUNE_BEAM}
+
+    @classmethod
+    def _opt(cls, gprune, gprune_num, chunk_frames):
+        return cls.Opt(cls._GPRUNE[gprune] if isinstance(gprune, str) else int(gprune), int(gprune_num), int(chunk_frames))
+
+    def __init__(self, eng: Engine, model: dict, gprune=None, gprune_num: int = 0, chunk_frames: int = 0):
+        if gprune is None:
+            GmmStreams.__init__(self, eng, model)
+            return
+        self.eng = eng
+        d, self._keep = self.make_desc(model)
+        self._create("jamd_gmm_ms_create_opt", eng.h, C.byref(d), C.byref(self._opt(gprune, gprune_num, chunk_frames)))
+        self._query()
+
+    def _query(self):
+        GmmStreams._query(self)
+        lib = load()
+        self.tmix_cap, self.nbook = lib.jamd_gmm_ms_tmix_cap(self.h), lib.jamd_gmm_ms_nbook(self.h)
+
+    @classmethod
+    def from_binhmm(cls, eng: Engine, path, gprune=None, gprune_num: int = 0, chunk_frames: int = 0):
+        """jamd_gmm_ms_load_binhmm_opt(): the codebook section and tmix pdfs of mkbinhmm's file included."""
+        if gprune is None:
+            return cls._load(eng, "jamd_gmm_ms_load_binhmm", [path])
+        return cls._load(eng, "jamd_gmm_ms_load_binhmm_opt", [path], C.byref(cls._opt(gprune, gprune_num, chunk_frames)))
+
+    def outprob_host(self, frames: np.ndarray, utt_off=None) -> np.ndarray:
+        if utt_off is None:
+            return GmmStreams.outprob_host(self, frames)
+        fr, off = _f32(frames), _i32(utt_off)
+        assert fr.ndim == 2 and fr.shape[1] == self.D and off[-1] == fr.shape[0]
+        out = np.empty((fr.shape[0], self.S), dtype=np.float32)
+        _call("jamd_gmm_ms_outprob_utts_host", self.h, fr.ctypes.data, off.ctypes.data, len(off) - 1, out.ctypes.data)
+        return out
+
+    def tmix_cache_host(self, frames: np.ndarray):
+        """Codebook cache (MIXCACHE) for every (frame, book) of one utterance: score, id, num."""
+        fr = _f32(frames)
+        T, cap, nbook = fr.shape[0], self.tmix_cap, self.nbook
+        d_fr = DevBuf(self.eng, fr.nbytes).upload(fr)
+        d_sc, d_id, d_n = (DevBuf(self.eng, 4 * T * nbook * c) for c in (cap, cap, 1))
+        _call("jamd_gmm_ms_tmix_cache_dev", self.h, d_fr.ptr, T, d_sc.ptr, d_id.ptr, d_n.ptr, None)
+        self.eng.sync()
+        return (d_sc.download((T, nbook, cap), np.float32), d_id.download((T, nbook, cap), np.int32),
+                d_n.download((T, nbook), np.int32))
 
 
 class Gms(_Handle):
